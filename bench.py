@@ -8,18 +8,27 @@ the same state, nothing is cached across steps.  Workload: 256^3 nodes per GPU
 (BASELINE configs[2]; weak scaling: N GPUs own a global grid of 256*(px,py,pz)).
 
     python bench.py [--gpus N] [--steps K] [--warmup W]      (N > 1: starts the N ranks itself)
+    python bench.py [--gpus N] [--steps K] [--warmup W] --full
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
 The headline storage is the default AIJ one: value-indexed (one index byte per 3x3 block into
 a dictionary of the matrix's distinct blocks, rebuilt by every assembly inside the step; exact
-values), its SpMV rows summed with fused multiply-adds (-mat_vi_fma 1, the default).  On one GPU
-the same storage with the bit-exact CPU-order rows (-mat_vi_fma 0) and the AIJ-split storage
-of the same matrix are measured after it (1 warmup + 1 step each, `variants` in the line;
-`--variants aij-vi-exact,aij-split,aij-blocks,sbaij` for more) while the `--budget` wall time
-lasts.  Also on one GPU, BASELINE config 5's path (128^3, the J2 Gauss-point law, three time
-steps of non-linear Newton, default AIJ storage with exception nodes) is run and reported as
-`config5` (`--config5 0` skips it).  Rank 0 prints ONE JSON line (the contract in the task
-statement / DESIGN.md §6) once the headline, the variants and the CPU baseline are measured.
+values), its SpMV rows summed with fused multiply-adds (-mat_vi_fma 1, the default).
+
+A plain run sets up, warms up, times the K steps of the headline and prints the line (the
+roofline figures in it come from the HIP events of those same steps).  `--dump-outputs DIR`
+also writes what the last timed step computed (u, du and the step's scalars) as DIR/<name>.npy.
+
+`--full` adds everything else the benchmark measures or checks, each in a run of its own after
+the headline: the true residual of the last solve (`check`); on one GPU the same storage with
+the bit-exact CPU-order rows (-mat_vi_fma 0) and the AIJ-split storage of the same matrix
+(1 warmup + 1 step each, `variants` in the line; `--variants
+aij-vi-exact,aij-split,aij-blocks,sbaij` for more) while the `--budget` wall time lasts; also on
+one GPU, BASELINE config 5's path (128^3, the J2 Gauss-point law, three time steps of non-linear
+Newton, default AIJ storage with exception nodes) reported as `config5` (`--config5 0` skips
+it), the uniformly plastic `bending` leg, and the CPU baseline under mpirun (`cpu_baseline`).
+Without `--full` those keys are in the line, empty.  Rank 0 prints ONE JSON line (the contract
+in DESIGN.md §6) once everything asked for is measured.
 """
 import argparse
 import json
@@ -278,7 +287,27 @@ def room_for_warmup(t_step, steps, args, rank, world):
     return ok
 
 
-def measure(argv, rank, world, comm_id, args, steps, warmup):
+DUMP_SAMPLE = 1 << 21  # entries of u and of du written by --dump-outputs (16 MiB each as float64)
+DUMP_SEED = 20240
+
+
+def dump_outputs(path, rank, world, res, its, rn, reason, u, du):
+    """--dump-outputs: what the last timed step handed to its caller, as float64 .npy files.
+    `step.npy` holds [|RES|, CG iterations, final residual norm, KSP reason]; `u.npy` and
+    `du.npy` hold this rank's owned entries, whole up to DUMP_SAMPLE entries, else the entries at
+    DUMP_SAMPLE sorted indices drawn once from a fixed seed (the same entries in every run of the
+    same arguments).  With several ranks every rank writes its own files (`u_rank3.npy`)."""
+    os.makedirs(path, exist_ok=True)
+    sfx = f"_rank{rank}" if world > 1 else ""
+    np.save(os.path.join(path, f"step{sfx}.npy"), np.array([res, its, rn, reason], dtype=np.float64))
+    for name, v in (("u", u), ("du", du)):
+        v = np.asarray(v, dtype=np.float64).ravel()
+        if v.size > DUMP_SAMPLE:
+            v = v[np.sort(np.random.default_rng(DUMP_SEED).integers(0, v.size, DUMP_SAMPLE))]
+        np.save(os.path.join(path, f"{name}{sfx}.npy"), v)
+
+
+def measure(argv, rank, world, comm_id, args, steps, warmup, dump_dir=None):
     """Setup + warmup + timed steps of one configuration; returns the timings of this rank.
     Timing mode only records HIP events on the compute stream (no host waits): one event pair
     per phase and per SpMV launch of the first 256 CG iterations of each solve."""
@@ -343,6 +372,8 @@ def measure(argv, rank, world, comm_id, args, steps, warmup):
     storage = m.get_info()
     spmv_avg_ms = tm["spmv_ms_total"] / max(tm["spmv_launches"], 1)
     spmv_bytes = tm["spmv_bytes_per_launch"]
+    if dump_dir:
+        dump_outputs(dump_dir, rank, world, res, its, rn, reason, m.u(), m.du())
     check = None
     if not args.no_check:
         # size-independent property: true residual of the solve, |A du - b| / |b| (collective)
@@ -422,6 +453,15 @@ def main():
     ap.add_argument("--cpu-grid", type=int, default=128, help="grid of the CPU baseline's full MPI step (0 = skip)")
     ap.add_argument("--cpu-ranks", type=int, default=0, help="MPI ranks of the CPU baseline (0 = every usable core)")
     ap.add_argument("--cpu-timeout", type=float, default=600.0, help="seconds the CPU baseline may take")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also run what takes runs of its own: the true-residual check, the "
+                         "storage variants, the config-5 and bending legs and the CPU baseline (--variants, "
+                         "--config5, --bending, --cpu-grid and --no-check choose among them; without --full none "
+                         "of them runs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed as DIR/<name>.npy (float64): "
+                         "step.npy = [|RES|, CG its, residual norm, KSP reason], u.npy and du.npy (whole up to "
+                         f"{DUMP_SAMPLE} entries, else a fixed seeded sample of that many)")
     ap.add_argument("--no-check", action="store_true")
     ap.add_argument("--mat-type", default="aij", choices=list(STORAGE_ARGS), help="matrix storage of the headline")
     ap.add_argument("--variants", default=None,
@@ -451,6 +491,8 @@ def main():
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if args.gpus is not None and args.gpus != world:  # (launch_ranks handled the no-launcher case)
         sys.exit(f"bench.py: --gpus {args.gpus} but WORLD_SIZE={world}")
+    if not args.full:  # a plain run: the headline alone
+        args.variants, args.config5, args.bending, args.cpu_grid, args.no_check = "", 0, 0, 0, True
     if args.variants is None:
         args.variants = "aij-vi-exact,aij-split" if world == 1 and args.mat_type == "aij" else ""
     rank = int(os.environ.get("RANK", "0"))
@@ -485,7 +527,8 @@ def main():
         dist.broadcast_object_list(obj, src=0)
         return obj[0]
 
-    r = measure(argv + STORAGE_ARGS[args.mat_type], rank, world, new_comm_id(), args, args.steps, args.warmup)
+    r = measure(argv + STORAGE_ARGS[args.mat_type], rank, world, new_comm_id(), args, args.steps, args.warmup,
+                dump_dir=args.dump_outputs)
     its, tm, info, check = r["its"], r["tm"], r["info"], r["check"]
     spmv_avg_ms, spmv_bytes, achieved, ms_step = r["spmv_avg_ms"], r["spmv_bytes"], r["achieved"], r["ms_step"]
     ndofs = 3 * NX * NY * NZ
@@ -547,6 +590,7 @@ def main():
             "warmup": args.warmup,
             "warmup_run": len(r["warmup_s"]),
             "ms_per_step": ms_step,
+            "full": args.full,
             "higher_is_better": True,
             "scaling": "weak",
             "vs_baseline": None,

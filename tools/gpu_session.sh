@@ -7,8 +7,8 @@
 #                  messages, std::terminate text) goes to the log instead of pytest's fd capture
 #   tests:<expr>   pytest -m gpu -k <expr>
 #   smoke          __graft_entry__.smoke()
-#   bench          the driver's command: python bench.py --steps 20 --warmup 5 (+ its wall time)
-#   bench-default  python bench.py
+#   bench          the whole line: python bench.py --full --steps 20 --warmup 5 (+ its wall time)
+#   bench-default  python bench.py --full
 #   rocprof        the headline under rocprofv3 --kernel-trace --stats (no variants / legs / CPU baseline)
 #   pmc            PMC HBM-traffic passes of the headline SpMV (tools/pmc_spmv.sh) + SQ passes (tools/pmc_vibm.sh)
 #   py:<script>    python tools/<script> (an A/B script; its arguments after a second colon, separated
@@ -56,10 +56,10 @@ for step in "$@"; do
       run smoke 180 "$base.log" python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" ;;
     bench)
       t0=$SECONDS
-      run bench 700 "$base.json" python bench.py --steps 20 --warmup 5
-      echo "$((SECONDS - t0)) s wall (python bench.py --steps 20 --warmup 5)" > "$base.wall" ;;
+      run bench 700 "$base.json" python bench.py --full --steps 20 --warmup 5
+      echo "$((SECONDS - t0)) s wall (python bench.py --full --steps 20 --warmup 5)" > "$base.wall" ;;
     bench-default)
-      run bench-default 600 "$base.json" python bench.py ;;
+      run bench-default 600 "$base.json" python bench.py --full ;;
     rocprof)
       run rocprof 600 "$base.json" rocprofv3 --kernel-trace --stats -d "gpurun_out/${TAG}_prof" -o run \
         --output-format csv -- python3 bench.py --variants '' --config5 0 --bending 0 --cpu-grid 0 ;;
