@@ -78,10 +78,12 @@ enum {
    lower triangle mirrored from it) */
 enum { MCX_MAT_AIJ = 0, MCX_MAT_SBAIJ = 1 };
 
-/* constitutive laws behind the Gauss-point callback (-mat_law elastic|plastic|external):
-   device isotropic elastic, device J2 plasticity (MicroPP material type 1), or an external law
-   registered through mcx_set_micropp / mcx_set_device_law / mcx_set_gp_stress+ctan */
-enum { MCX_LAW_ELASTIC = 0, MCX_LAW_PLASTIC = 1, MCX_LAW_EXTERNAL = 2 };
+/* constitutive laws behind the Gauss-point callback (-mat_law elastic|plastic|external|micro):
+   device isotropic elastic, device J2 plasticity (MicroPP material type 1), an external law
+   registered through mcx_set_micropp / mcx_set_device_law / mcx_set_gp_stress+ctan, or the linear
+   two-phase micro cell (-micro_n, -micro_type, -micro_mat_1/2) homogenised on the device: one
+   tangent C_hom, sigma = C_hom eps at every Gauss point (mcx_micro_get_ctan) */
+enum { MCX_LAW_ELASTIC = 0, MCX_LAW_PLASTIC = 1, MCX_LAW_EXTERNAL = 2, MCX_LAW_MICRO = 3 };
 
 typedef struct {
   int64_t NX, NY, NZ;          /* -da_grid_x/y/z          (default 40 3 40, include/macroc.h:44-46) */
@@ -103,8 +105,9 @@ typedef struct {
   int device;                  /* HIP device of this rank (-1: rank % device count) */
   int ksp_monitor;             /* -ksp_monitor: keep the residual history */
   int mat_type;                /* -dm_mat_type aij|sbaij  (MCX_MAT_AIJ) */
-  int mat_law;                 /* -mat_law elastic|plastic (MCX_LAW_ELASTIC; plastic = J2 with
-                                  micro_mat_1's Sy, Ka: MicroPP material type 1) */
+  int mat_law;                 /* -mat_law elastic|plastic|external|micro (MCX_LAW_ELASTIC; plastic = J2
+                                  with micro_mat_1's Sy, Ka: MicroPP material type 1; micro = the
+                                  two-phase micro cell homogenised on the device) */
   int mat_aij_split;           /* -mat_aij_split 0|1 (1): hold the AIJ matrix exactly as upper blocks +
                                   bf16 lower corrections when all are exact (else plain AIJ blocks);
                                   0: AIJ blocks, rows summed in the reference's MatMult order (inode column pairs) (bit-exact SpMV) */
@@ -223,7 +226,8 @@ int mcx_get_info(void* ctx, mcx_info* info);
    context's device without a communicator.  Any pointer may be NULL. */
 int mcx_comm_info(void* ctx, int* comm_ranks, int* comm_rank, int* device);
 
-/* Gauss-point constitutive model (micropp_C_material_set(id,E,nu,Sy,Ka,type)) */
+/* Gauss-point constitutive model (micropp_C_material_set(id,E,nu,Sy,Ka,type)).  id 1 has to equal
+   id 0 except under -mat_law micro, where ids 0 and 1 are the micro cell's two phases */
 int mcx_material_set(void* ctx, int id, double E, double nu, double Sy, double Ka, int type);
 
 /* ---- the MicroPP Gauss-point callback boundary (-mat_law external) ----
@@ -275,6 +279,28 @@ int mcx_set_device_law(void* ctx, const mcx_device_law* law);
 int mcx_set_gp_stress(void* ctx, const double* host /* [ngp][6] */);
 int mcx_set_gp_ctan(void* ctx, const double* host /* [ngp][36] */);
 int mcx_get_gp_strain(void* ctx, double* host /* [ngp][6] */);
+
+/* ---- the micro-scale cell (-mat_law micro) ----
+ * The unit cube with micro_n nodes per edge (2 <= micro_n <= 10), ne = micro_n - 1 Q1 hexahedra per
+ * edge, 2x2x2 Gauss points, physical B.  Material 0 is micro_mat_1, material 1 micro_mat_2 (E, nu;
+ * isotropic elastic, Sy and Ka unused).  Element (i, j, k), 0 <= i, j, k < ne, is of material 1 iff
+ *   micro_type 0 (centred sphere, radius 0.5): (2i+1-ne)^2 + (2j+1-ne)^2 + (2k+1-ne)^2 < ne^2
+ *   micro_type 1 (flat layer in y):            2j+1 < ne
+ * in integer arithmetic.  For each Voigt component l the boundary nodes get u = E_l x (unit
+ * strain; shear cases E_ab = E_ba = 1/2) and the interior solves K_ii u_i = -K_ib u_b by
+ * Jacobi-preconditioned CG from zero until the preconditioned residual norm is at most
+ * "micro_rtol" (mcx_set_option, default 1e-12) times its first value, or "micro_max_it"
+ * iterations (default 10 x interior dofs) have run, which fails the calling entry.  Column l of C
+ * is the volume average of the Gauss-point stresses; C_hom = (C + C^T) / 2.  It is computed on
+ * the device at the first mcx_homogenize, mcx_assembly_jac or mcx_micro_get_ctan after mcx_init
+ * and again after mcx_material_set or a micro_* option changed it; every context of a multi-rank
+ * run computes its own, bit-identical copy. */
+/* C_hom (row major, C[k*6+l]) and, per load case, the CG iterations and the final relative
+   preconditioned residual norm.  Any pointer may be NULL. */
+int mcx_micro_get_ctan(void* ctx, double C[36], int its[6], double rnorm[6]);
+/* the elements' materials (0 / 1), x fastest: phase[i + ne*(j + ne*k)]; *n in: capacity, out:
+   count ne^3 (phase may be NULL to query the count) */
+int mcx_micro_get_phase(void* ctx, unsigned char* phase, int64_t* n);
 
 double mcx_get_displacement(void* ctx, int time_s);
 int mcx_zero_u(void* ctx);                 /* VecZeroEntries(u)  src/init.c:103 */
@@ -336,7 +362,8 @@ int mcx_get_ksp_history(void* ctx, double* hist, int64_t* n);
 int mcx_set_timing(void* ctx, int on);
 int mcx_get_timing(void* ctx, mcx_timing* t);
 int mcx_synchronize(void* ctx);
-/* tuning knobs ("spmv_subl": lines per sub-slab of the SpMV sweep, 0 = whole XCD slab) and a
+/* tuning knobs ("spmv_subl": lines per sub-slab of the SpMV sweep, 0 = whole XCD slab; "micro_rtol",
+   "micro_max_it": the micro cell's CG, -mat_law micro) and a
    device-only SpMV timer (iters launches on the current search direction, HIP events) */
 int mcx_set_option(void* ctx, const char* name, double value);
 int mcx_time_spmv(void* ctx, int iters, double* avg_ms);

@@ -40,9 +40,10 @@ EXPORTS = [
     "mcx_owned_dofs", "mcx_dump_csr", "mcx_dump_dirichlet", "mcx_spmv", "mcx_get_ksp_history",
     "mcx_set_timing", "mcx_get_timing", "mcx_synchronize", "mcx_set_option", "mcx_time_spmv",
     "mcx_set_micropp", "mcx_set_device_law", "mcx_set_gp_stress", "mcx_set_gp_ctan", "mcx_get_gp_strain",
+    "mcx_micro_get_ctan", "mcx_micro_get_phase",
 ]
 
-LAWS = {"elastic": 0, "plastic": 1, "external": 2}
+LAWS = {"elastic": 0, "plastic": 1, "external": 2, "micro": 3}
 
 
 class Opts(C.Structure):
@@ -183,6 +184,8 @@ def lib():
     L.mcx_set_device_law.argtypes = [vp, C.POINTER(DeviceLaw)]
     for fn in ("mcx_set_gp_stress", "mcx_set_gp_ctan", "mcx_get_gp_strain"):
         getattr(L, fn).argtypes = [vp, d]
+    L.mcx_micro_get_ctan.argtypes = [vp, d, C.POINTER(C.c_int), d]
+    L.mcx_micro_get_phase.argtypes = [vp, C.POINTER(C.c_ubyte), i64]
     _LIB = L
     return L
 
@@ -427,6 +430,24 @@ class Macroc:
     def gp_strain(self):
         """strains of the callback box, [ngp][6] in gpi order."""
         return self._get("mcx_get_gp_strain", self.ngp * 6).reshape(-1, 6)
+
+    # ---- the micro-scale cell (-mat_law micro)
+    def micro_ctan(self):
+        """(C_hom [6][6], CG iterations [6], final relative preconditioned residual [6]) of the
+        two-phase micro cell, one entry per unit-strain load case (xx, yy, zz, xy, xz, yz)."""
+        Ch, its, rn = np.zeros(36), (C.c_int * 6)(), np.zeros(6)
+        _check(lib().mcx_micro_get_ctan(self._ctx, _dp(Ch), its, _dp(rn)), "mcx_micro_get_ctan")
+        return Ch.reshape(6, 6), list(its), rn
+
+    def micro_phase(self):
+        """material (0 / 1) of every micro element, [k][j][i] (x fastest)."""
+        n = C.c_int64(0)
+        _check(lib().mcx_micro_get_phase(self._ctx, None, C.byref(n)), "mcx_micro_get_phase")
+        ph = np.zeros(n.value, dtype=np.uint8)
+        _check(lib().mcx_micro_get_phase(self._ctx, ph.ctypes.data_as(C.POINTER(C.c_ubyte)), C.byref(n)),
+               "mcx_micro_get_phase")
+        ne = round(n.value ** (1.0 / 3.0))
+        return ph.reshape(ne, ne, ne)
 
     # ---- data access (owned rows, PETSc-local order)
     def _get(self, fn, n):

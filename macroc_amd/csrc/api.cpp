@@ -68,6 +68,10 @@ static void elastic_C(double E, double nu, double C[36]) {
   for (int a = 3; a < 6; a++) C[a * 6 + a] = mu;
 }
 
+// laws that hand over a tangent per Gauss point (ctan, element matrices per element); the elastic
+// law and the micro law (one homogenised tangent) have one tangent in the kernel argument
+static bool gp_tangent_law(int law) { return law == MCX_LAW_PLASTIC || law == MCX_LAW_EXTERNAL; }
+
 // phase timer: an event pair on the compute stream, recorded without any host wait (the
 // timed steps are not serialised by the instrumentation); mcx_get_timing resolves the last pair
 enum { PH_STRAINS, PH_HOMOG, PH_RES, PH_JAC, PH_SOLVE, PH_UPDATE };
@@ -91,7 +95,7 @@ static int free_ctx(Ctx* c) {
   if (c->comm_stream) (void)hipStreamSynchronize(c->comm_stream);
   if (c->x_stream) (void)hipStreamSynchronize(c->x_stream);
   if (c->f_stream) (void)hipStreamSynchronize(c->f_stream);
-  void* ptrs[] = {c->hist_old, c->hist_new, c->ftrial, c->b, c->du, c->r, c->z, c->w, c->jix, c->jdd, c->V, c->U, c->D, c->d_mask, c->vi_idx, c->wd, c->vi_dict, c->vi_keys, c->vi_slot, c->vi_ctl, c->vi_bdict, c->eps, c->sig, c->ctan, c->Ke,
+  void* ptrs[] = {c->micro_out, c->hist_old, c->hist_new, c->ftrial, c->b, c->du, c->r, c->z, c->w, c->jix, c->jdd, c->V, c->U, c->D, c->d_mask, c->vi_idx, c->wd, c->vi_dict, c->vi_keys, c->vi_slot, c->vi_ctl, c->vi_bdict, c->eps, c->sig, c->ctan, c->Ke,
                   c->vib_keys, c->vib_ctl, c->vib_pos, c->ke_uni, c->xdone, c->esc_node, c->esc_res, c->esc_slot, c->elem_plain, c->cref, c->vi_xslot,
                   c->vi_xlist, c->vi_xcnt, c->vi_exc, c->st_coef, c->st_ids, c->st_slot, c->st_list, c->st_cnt, c->st_mask,
                   c->partials, c->red, c->red_loc, c->cg, c->hist, c->tmp, c->halo.d_send_idx,
@@ -208,7 +212,7 @@ static int init_ctx(Ctx& c, const mcx_opts* o, int rank, int nranks, const void*
   c.dinv = c.jdd + 3 * VI_MAX;
   // per-GP tangent: only laws that hand one over (the isotropic elastic C is a kernel argument)
   c.partials2 = c.partials + c.partials_cap / 2;
-  if (o->mat_law != MCX_LAW_ELASTIC &&
+  if (gp_tangent_law(o->mat_law) &&
       ((rc = dalloc(c, &c.ctan, 36 * 8 * E)) || (rc = dalloc(c, &c.Ke, (int64_t)576 * E))))
     return rc;
   if (o->mat_law == MCX_LAW_PLASTIC &&
@@ -218,7 +222,7 @@ static int init_ctx(Ctx& c, const mcx_opts* o, int rank, int nranks, const void*
   if (c.aij_split) MCX_HIP(hipMalloc(&c.d_mask, 16 * sizeof(unsigned)));
   MCX_HIP(hipHostMalloc((void**)&c.h_cg, sizeof(CgState) * 2, hipHostMallocDefault));
   std::memset(c.h_cg, 0, sizeof(CgState) * 2);
-  if (o->micro_n != 2 && o->mat_law != MCX_LAW_EXTERNAL && rank == 0)
+  if (o->micro_n != 2 && o->mat_law != MCX_LAW_EXTERNAL && o->mat_law != MCX_LAW_MICRO && rank == 0)
     std::fprintf(stderr,
                  "WARNING! -micro_n %d has no effect: the device Gauss-point laws have no micro-scale FE problem "
                  "(MicroPP's FE2 solver is out of scope); it sizes an external MicroPP (-mat_law external, "
@@ -230,6 +234,17 @@ static int init_ctx(Ctx& c, const mcx_opts* o, int rank, int nranks, const void*
   c.mat.Sy = o->micro_mat_1[2];
   c.mat.Ka = o->micro_mat_1[3];
   elastic_C(c.mat.E, c.mat.nu, c.mat.C);
+  if (o->mat_law == MCX_LAW_MICRO) {  // C_hom replaces mat.C at its first use (ensure_micro)
+    if ((rc = dalloc(c, &c.micro_out, 6 * MICRO_OUT))) return rc;
+    c.micro.n = o->micro_n;
+    c.micro.type = o->micro_type;
+    c.micro.E[0] = o->micro_mat_1[0];
+    c.micro.nu[0] = o->micro_mat_1[1];
+    c.micro.E[1] = o->micro_mat_2[0];
+    c.micro.nu[1] = o->micro_mat_2[1];
+    c.micro.rtol = 1e-12;
+    c.micro_dirty = true;
+  }
   c.nnz_local = count_nnz_rows(c, g.xs, g.ys, g.zs, g.nx, g.ny, g.nz);
   c.nnz_global = count_nnz_rows(c, 0, 0, 0, o->NX, o->NY, o->NZ);
   c.nupper_local = count_upper_values(c);
@@ -452,12 +467,15 @@ int mcx_parse_args(mcx_opts* o, int argc, const char* const* argv) try {
     }
     if (!std::strcmp(k, "-mat_ignore_lower_triangular")) continue;
     if (!std::strcmp(k, "-mat_law")) {
-      if (!v || (std::strcmp(v, "elastic") && std::strcmp(v, "plastic") && std::strcmp(v, "external"))) {
-        set_error(std::string("-mat_law: elastic, plastic or external, got ") + (v ? v : "(none)"));
+      if (!v || (std::strcmp(v, "elastic") && std::strcmp(v, "plastic") && std::strcmp(v, "external") &&
+                 std::strcmp(v, "micro"))) {
+        set_error(std::string("-mat_law: elastic, plastic, external or micro, got ") + (v ? v : "(none)"));
         return 2;
       }
       o->mat_law = !std::strcmp(v, "plastic") ? MCX_LAW_PLASTIC
-                   : !std::strcmp(v, "external") ? MCX_LAW_EXTERNAL : MCX_LAW_ELASTIC;
+                   : !std::strcmp(v, "external") ? MCX_LAW_EXTERNAL
+                   : !std::strcmp(v, "micro")    ? MCX_LAW_MICRO
+                                                 : MCX_LAW_ELASTIC;
       a++;
       continue;
     }
@@ -679,6 +697,22 @@ int mcx_material_set(void* ctx, int id, double E, double nu, double Sy, double K
   (void)Sy;
   (void)Ka;
   (void)type;
+  if (c.mat.law == MCX_LAW_MICRO) {  // the micro cell's two phases; Sy, Ka unused (linear micro problem)
+    if (id != 0 && id != 1) {
+      set_error("mcx_material_set: -mat_law micro has materials 0 and 1");
+      return 3;
+    }
+    if (id == 0) {
+      c.mat.E = E;
+      c.mat.nu = nu;
+      c.mat.Sy = Sy;
+      c.mat.Ka = Ka;
+    }
+    c.micro.E[id] = E;
+    c.micro.nu[id] = nu;
+    c.micro_dirty = true;
+    return 0;
+  }
   if (id == 0) {
     c.mat.E = E;
     c.mat.nu = nu;
@@ -727,6 +761,52 @@ int mcx_set_strains(void* ctx) try {
   MCX_HIP(hipGetLastError());
   return 0;
 } MCX_CATCH
+
+// -mat_law micro: C_hom of the two-phase cell into mat.C when it is not current: six
+// unit-strain solves in one launch (k_micro_rve), column l = block l's average stress, then
+// C_hom = (C + C^T) / 2 on the host (exactly symmetric; the same bits in every context)
+static int ensure_micro(Ctx& c) {
+  if (c.mat.law != MCX_LAW_MICRO || !c.micro_dirty) return 0;
+  MicroArgs m = c.micro;
+  if (m.n < 2 || m.n > MICRO_NMAX) {
+    set_error("-mat_law micro: -micro_n " + std::to_string(m.n) + " outside the supported range 2 <= micro_n <= " +
+              std::to_string(MICRO_NMAX) + " (the cell's CG state has to fit one CU's LDS)");
+    return 31;
+  }
+  if (m.type != 0 && m.type != 1) {
+    set_error("-mat_law micro: -micro_type " + std::to_string(m.type) +
+              " is not implemented (0: centred sphere, 1: flat layer in y)");
+    return 32;
+  }
+  const int interior = 3 * (m.n - 2) * (m.n - 2) * (m.n - 2);
+  m.max_it = c.micro_max_it > 0 ? c.micro_max_it : 10 * interior;
+  launch_micro_rve(c, m);
+  MCX_HIP(hipGetLastError());
+  double h[6 * MICRO_OUT];
+  MCX_HIP(hipMemcpyAsync(h, c.micro_out, sizeof(h), hipMemcpyDeviceToHost, c.stream));
+  MCX_HIP(hipStreamSynchronize(c.stream));
+  static const char* const kVoigt[6] = {"xx", "yy", "zz", "xy", "xz", "yz"};
+  double Cc[36];
+  for (int l = 0; l < 6; l++) {
+    const double* o = h + MICRO_OUT * l;
+    c.micro_its[l] = (int)o[6];
+    c.micro_rnorm[l] = o[7];
+    if (o[8] == 0.) {
+      char buf[256];
+      std::snprintf(buf, sizeof(buf),
+                    "-mat_law micro: the micro cell's CG did not converge for load case %d (unit strain component "
+                    "%s): %d iterations, relative preconditioned residual %.3e > micro_rtol %.3e",
+                    l, kVoigt[l], c.micro_its[l], o[7], m.rtol);
+      set_error(buf);
+      return 33;
+    }
+    for (int k = 0; k < 6; k++) Cc[k * 6 + l] = o[k];
+  }
+  for (int k = 0; k < 6; k++)
+    for (int l = 0; l < 6; l++) c.mat.C[k * 6 + l] = 0.5 * (Cc[k * 6 + l] + Cc[l * 6 + k]);
+  c.micro_dirty = false;
+  return 0;
+}
 
 // -mat_law external: the registered law fills sig and ctan from eps (see macroc_amd.h)
 static int external_homogenize(Ctx& c) {
@@ -779,6 +859,7 @@ int mcx_homogenize(void* ctx) try {
   CTX(ctx);
   PhaseTimer t(c, PH_HOMOG);
   if (c.mat.law == MCX_LAW_EXTERNAL) return external_homogenize(c);
+  if (int rc = ensure_micro(c)) return rc;
   launch_homogenize(c);
   MCX_HIP(hipGetLastError());
   return 0;
@@ -862,6 +943,60 @@ int mcx_get_gp_strain(void* ctx, double* host) try {
   return 0;
 } MCX_CATCH
 
+int mcx_micro_get_ctan(void* ctx, double* C, int* its, double* rnorm) try {
+  MCX_ENTRY();
+  GUARD(ctx);
+  CTX(ctx);
+  if (c.mat.law != MCX_LAW_MICRO) {
+    set_error("mcx_micro_get_ctan: the context was created without -mat_law micro");
+    return 7;
+  }
+  if (int rc = ensure_micro(c)) return rc;
+  for (int q = 0; q < 36 && C; q++) C[q] = c.mat.C[q];
+  for (int l = 0; l < 6; l++) {
+    if (its) its[l] = c.micro_its[l];
+    if (rnorm) rnorm[l] = c.micro_rnorm[l];
+  }
+  return 0;
+} MCX_CATCH
+
+int mcx_micro_get_phase(void* ctx, unsigned char* phase, int64_t* n) try {
+  MCX_ENTRY();
+  GUARD(ctx);
+  CTX(ctx);
+  if (c.mat.law != MCX_LAW_MICRO) {
+    set_error("mcx_micro_get_phase: the context was created without -mat_law micro");
+    return 7;
+  }
+  const int mn = c.micro.n, ne = mn - 1, type = c.micro.type;
+  if (mn < 2 || mn > MICRO_NMAX) {
+    set_error("-mat_law micro: -micro_n " + std::to_string(mn) + " outside the supported range 2 <= micro_n <= " +
+              std::to_string(MICRO_NMAX));
+    return 31;
+  }
+  if (type != 0 && type != 1) {
+    set_error("-mat_law micro: -micro_type " + std::to_string(type) +
+              " is not implemented (0: centred sphere, 1: flat layer in y)");
+    return 32;
+  }
+  if (!n) {
+    set_error("mcx_micro_get_phase: n is required");
+    return 1;
+  }
+  const int64_t cnt = (int64_t)ne * ne * ne;
+  if (phase) {
+    if (*n < cnt) {
+      set_error("mcx_micro_get_phase: capacity " + std::to_string(*n) + " < " + std::to_string(cnt) + " elements");
+      return 2;
+    }
+    for (int k = 0; k < ne; k++)
+      for (int j = 0; j < ne; j++)
+        for (int i = 0; i < ne; i++) phase[i + ne * (j + ne * k)] = (unsigned char)micro_phase(type, ne, i, j, k);
+  }
+  *n = cnt;
+  return 0;
+} MCX_CATCH
+
 int mcx_assembly_res(void* ctx, double* norm2) try {
   MCX_ENTRY();
   GUARD(ctx);
@@ -914,7 +1049,8 @@ int mcx_assembly_jac(void* ctx) try {
   CTX(ctx);
   PhaseTimer t(c, PH_JAC);
   int rc;
-  const bool table = c.mat.law != MCX_LAW_ELASTIC;
+  if ((rc = ensure_micro(c))) return rc;
+  const bool table = gp_tangent_law(c.mat.law);
   const bool try_vi = c.o.mat_type == MCX_MAT_AIJ && c.aij_vi && !c.vi_declined;
   // a per-GP-tangent law headed for the value-indexed storage with exception nodes: kref and the
   // non-plain elements' matrices only (the value-indexed build needs no other element matrix)
@@ -958,7 +1094,7 @@ int mcx_assembly_jac(void* ctx) try {
       launch_gather_matrix(c);
       // a per-GP-tangent law keeps its inexact (or refused dense) corrections: later assemblies
       // go straight to blocks
-      c.split_declined = c.mat.law != MCX_LAW_ELASTIC;
+      c.split_declined = gp_tangent_law(c.mat.law);
     }
   } else {
     if ((rc = ensure_V(c))) return rc;
@@ -1517,6 +1653,20 @@ int mcx_set_option(void* ctx, const char* name, double value) try {
   MCX_ENTRY();
   GUARD(ctx);
   CTX(ctx);
+  if (!std::strcmp(name, "micro_rtol")) {  // -mat_law micro: the cell's CG stopping rule; C_hom is recomputed
+    if (!(value > 0.)) {
+      set_error("micro_rtol: > 0");
+      return 1;
+    }
+    c.micro.rtol = value;
+    c.micro_dirty = true;
+    return 0;
+  }
+  if (!std::strcmp(name, "micro_max_it")) {  // 0: 10 x the interior dofs
+    c.micro_max_it = std::max(0, (int)value);
+    c.micro_dirty = true;
+    return 0;
+  }
   if (!std::strcmp(name, "spmv_subl")) {
     const int old = c.spmv_subl;
     c.spmv_subl = (int)value;

@@ -558,6 +558,311 @@ __global__ void k_elastic_ke(Geo g, Material mat, double* __restrict__ keu) {
   for (int q = 0; q < 9; q++) keu[t * 9 + q] = ke[q];
 }
 
+// -mat_law micro: one homogenised tangent for every Gauss point, so one element matrix as for the
+// elastic law, but C_hom is a general symmetric 6x6 (orthotropic cells, CG noise in the entries
+// an isotropic C has as zeros): ke_block with all 36 C entries.  Zero B terms are still skipped;
+// gp, k, l ascending and ((B*C)*B)*wg as in ke_body, so the matrix equals bit for bit what the
+// per-element table path (k_element_ke) builds from the same tangent at every Gauss point.
+__device__ __forceinline__ void ke_block_full(const Geo& g, const Material& mat, int a, int bn, double (&ke)[9]) {
+#pragma unroll
+  for (int q = 0; q < 9; q++) ke[q] = 0.;
+  const double wg = g.wg;
+  for (int gp = 0; gp < 8; gp++) {
+    double Ba[3][3], Bb[3][3];
+#pragma unroll
+    for (int r = 0; r < 3; r++)
+#pragma unroll
+      for (int q = 0; q < 3; q++) {
+        Ba[r][q] = cB[gp][krow(r, q)][3 * a + r];
+        Bb[r][q] = cB[gp][krow(r, q)][3 * bn + r];
+      }
+#pragma unroll
+    for (int k = 0; k < 6; k++)
+#pragma unroll
+      for (int l = 0; l < 6; l++) {
+        const double Ckl = mat.C[k * 6 + l];
+#pragma unroll
+        for (int r = 0; r < 3; r++) {
+          if (!kin(r, k)) continue;
+          const double t0 = Ba[r][kpos(r, k)] * Ckl;
+#pragma unroll
+          for (int c = 0; c < 3; c++) {
+            if (!kin(c, l)) continue;
+            ke[r * 3 + c] += t0 * Bb[c][kpos(c, l)] * wg;
+          }
+        }
+      }
+  }
+}
+
+__global__ void k_micro_ke(Geo g, Material mat, double* __restrict__ keu) {
+  const int t = threadIdx.x;
+  if (t >= 64) return;
+  double ke[9];
+  ke_block_full(g, mat, t >> 3, t & 7, ke);
+#pragma unroll
+  for (int q = 0; q < 9; q++) keu[t * 9 + q] = ke[q];
+}
+
+// ---------------------------------------------------------------------------- micro-scale RVE
+// -mat_law micro: the two-phase unit cell of n^3 nodes / (n-1)^3 Q1 hexahedra
+// (2x2x2 Gauss, physical B), one workgroup per unit-strain load case l = 0..5 (Voigt, engineering
+// shear).  Boundary nodes carry u = E_l x, the interior solves K_ii u_i = -K_ib u_b by
+// Jacobi-preconditioned CG from a zero guess; block l leaves the volume average of the
+// Gauss-point stresses (column l of C), its iteration count and its final relative
+// preconditioned-residual norm.  The whole CG state stays in LDS: x, r, p, Ap and the inverse
+// diagonal (3 n^3 doubles each), the two phases' 24x24 element matrices, the shape-function
+// gradients and the phase bytes.  The operator is applied matrix-free, node by node: a node
+// gathers from its (at most 8) elements in a fixed order, no atomics; every reduction is a fixed
+// tree (wave butterfly, then the 16 wave sums in ascending order), so the result is the same bits
+// in every run and in every context that computes its own copy.
+__device__ __forceinline__ void micro_reduce2(double& a, double& b, double* sred) {
+  a = wave_sum(a);
+  b = wave_sum(b);
+  const int w = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) {
+    sred[2 * w] = a;
+    sred[2 * w + 1] = b;
+  }
+  __syncthreads();
+  double ra = 0., rb = 0.;
+  for (int q = 0; q < MICRO_TPB / 64; q++) {
+    ra += sred[2 * q];
+    rb += sred[2 * q + 1];
+  }
+  __syncthreads();
+  a = ra;
+  b = rb;
+}
+
+__device__ __forceinline__ double micro_iso_C(double E, double nu, int k, int l) {
+  const double lam = E * nu / ((1. + nu) * (1. - 2. * nu));
+  const double mu = E / (2. * (1. + nu));
+  if (k < 3 && l < 3) return lam + (k == l ? 2. * mu : 0.);
+  return k == l ? mu : 0.;
+}
+
+// B[k][3a + r] of the micro element from the gradient table dn[a][d] of one Gauss point
+__device__ __forceinline__ double micro_B(const double* dn, int k, int a, int r) {
+  if (k < 3) return k == r ? dn[a * 3 + r] : 0.;
+  const int p = k == 5 ? 1 : 0, q = k == 3 ? 1 : 2;  // xy: (0, 1), xz: (0, 2), yz: (1, 2)
+  if (r == p) return dn[a * 3 + q];
+  if (r == q) return dn[a * 3 + p];
+  return 0.;
+}
+
+// y = (K v) at node (i, j, k): its elements in the order oz, oy, ox descending offsets = ascending
+// element index, each element's 8 nodes ascending; local node a = ox + 2 oy + 4 oz
+__device__ __forceinline__ void micro_apply(const double* __restrict__ ske, const unsigned char* __restrict__ sph,
+                                            const double* __restrict__ v, int n, int i, int j, int k, double (&y)[3]) {
+  const int ne = n - 1;
+  y[0] = y[1] = y[2] = 0.;
+#pragma unroll 1
+  for (int oz = 1; oz >= 0; oz--) {
+    const int ek = k - oz;
+    if (ek < 0 || ek >= ne) continue;
+#pragma unroll 1
+    for (int oy = 1; oy >= 0; oy--) {
+      const int ej = j - oy;
+      if (ej < 0 || ej >= ne) continue;
+#pragma unroll 1
+      for (int ox = 1; ox >= 0; ox--) {
+        const int ei = i - ox;
+        if (ei < 0 || ei >= ne) continue;
+        const int a = ox + 2 * oy + 4 * oz;
+        const double* row = ske + 576 * sph[ei + ne * (ej + ne * ek)] + 72 * a;
+#pragma unroll 1
+        for (int b = 0; b < 8; b++) {
+          const int nb = (ei + (b & 1)) + n * ((ej + (b >> 1 & 1)) + n * (ek + (b >> 2)));
+          const double v0 = v[3 * nb], v1 = v[3 * nb + 1], v2 = v[3 * nb + 2];
+#pragma unroll
+          for (int r = 0; r < 3; r++) {
+            const double* kr = row + 24 * r + 3 * b;
+            y[r] += kr[0] * v0;
+            y[r] += kr[1] * v1;
+            y[r] += kr[2] * v2;
+          }
+        }
+      }
+    }
+  }
+}
+
+__global__ __launch_bounds__(MICRO_TPB) void k_micro_rve(MicroArgs m, double* __restrict__ out) {
+  __shared__ double sx[MICRO_DOFS], sr[MICRO_DOFS], sp[MICRO_DOFS], sq[MICRO_DOFS], sd[MICRO_DOFS];
+  __shared__ double ske[2 * 576];
+  __shared__ double sdn[8 * 24];  // [gp][a][d] physical shape-function gradients
+  __shared__ double sred[2 * (MICRO_TPB / 64)];
+  __shared__ unsigned char sph[(MICRO_NMAX - 1) * (MICRO_NMAX - 1) * (MICRO_NMAX - 1)];
+  const int tid = threadIdx.x, lc = blockIdx.x;
+  const int n = m.n, ne = n - 1, nn = n * n * n, ndof = 3 * nn, nel = ne * ne * ne;
+  if (n < 2 || n > MICRO_NMAX || lc >= 6) return;  // (the host refuses these sizes before the launch)
+  const double detJ = 1. / (8. * (double)nel);  // (h / 2)^3, h = 1 / ne
+
+  for (int e = tid; e < nel; e += MICRO_TPB)
+    sph[e] = (unsigned char)micro_phase(m.type, ne, e % ne, (e / ne) % ne, e / (ne * ne));
+  for (int t = tid; t < 8 * 24; t += MICRO_TPB) {
+    const int gp = t / 24, a = (t % 24) / 3, d = t % 3;
+    const double gq = 0.57735026918962576451;
+    double v = 0.125 * (2. * (double)ne);
+    for (int q = 0; q < 3; q++) {
+      const double sa = (a >> q & 1) ? 1. : -1., xi = (gp >> q & 1) ? gq : -gq;
+      v *= (q == d) ? sa : (1. + sa * xi);
+    }
+    sdn[t] = v;
+  }
+  __syncthreads();
+  // the two phases' element matrices: Ke[i][j] = sum_gp sum_k sum_l B[k][i] C[k][l] B[l][j] detJ
+  for (int t = tid; t < 2 * 576; t += MICRO_TPB) {
+    const int ph = t / 576, i = (t % 576) / 24, j = t % 24;
+    double s = 0.;
+#pragma unroll 1
+    for (int gp = 0; gp < 8; gp++)
+#pragma unroll 1
+      for (int k = 0; k < 6; k++) {
+        const double bk = micro_B(sdn + 24 * gp, k, i / 3, i % 3);
+        if (bk == 0.) continue;
+#pragma unroll 1
+        for (int l = 0; l < 6; l++)
+          s += bk * micro_iso_C(ph ? m.E[1] : m.E[0], ph ? m.nu[1] : m.nu[0], k, l) * micro_B(sdn + 24 * gp, l, j / 3, j % 3) * detJ;
+      }
+    ske[t] = s;
+  }
+  __syncthreads();
+  // u = E_l x on the boundary, 0 inside; the Jacobi inverse diagonal of the interior dofs
+  for (int nd = tid; nd < nn; nd += MICRO_TPB) {
+    const int i = nd % n, j = (nd / n) % n, k = nd / (n * n);
+    const bool bnd = i == 0 || j == 0 || k == 0 || i == ne || j == ne || k == ne;
+    const double X[3] = {(double)i / (double)ne, (double)j / (double)ne, (double)k / (double)ne};
+    double u[3] = {0., 0., 0.};
+    if (bnd) {  // u_r = sum_d E_l[r][d] x_d: E_l[l][l] = 1 (l < 3), else E_l[p][q] = E_l[q][p] = 1/2
+      const int p = lc == 5 ? 1 : 0, q = lc == 3 ? 1 : 2;  // xy: (0, 1), xz: (0, 2), yz: (1, 2)
+#pragma unroll
+      for (int r = 0; r < 3; r++)
+#pragma unroll
+        for (int d = 0; d < 3; d++) {
+          const double e = lc < 3 ? ((r == lc && d == lc) ? 1. : 0.) : (((r == p && d == q) || (r == q && d == p)) ? 0.5 : 0.);
+          if (e != 0.) u[r] = e * X[d];
+        }
+    }
+    double dg[3] = {0., 0., 0.};
+#pragma unroll 1
+    for (int oz = 1; oz >= 0; oz--)
+#pragma unroll 1
+      for (int oy = 1; oy >= 0; oy--)
+#pragma unroll 1
+        for (int ox = 1; ox >= 0; ox--) {
+          const int ei = i - ox, ej = j - oy, ek = k - oz;
+          if (ei < 0 || ej < 0 || ek < 0 || ei >= ne || ej >= ne || ek >= ne) continue;
+          const int a = ox + 2 * oy + 4 * oz;
+          const double* ke = ske + 576 * sph[ei + ne * (ej + ne * ek)];
+#pragma unroll
+          for (int r = 0; r < 3; r++) dg[r] += ke[(3 * a + r) * 25];
+        }
+#pragma unroll
+    for (int r = 0; r < 3; r++) {
+      sx[3 * nd + r] = u[r];
+      sd[3 * nd + r] = bnd ? 0. : 1. / dg[r];
+    }
+  }
+  __syncthreads();
+  // r = -(K x) on the interior (x = 0 there), p = z = D^-1 r
+  double rz = 0., zz = 0.;
+  for (int nd = tid; nd < nn; nd += MICRO_TPB) {
+    const int i = nd % n, j = (nd / n) % n, k = nd / (n * n);
+    const bool bnd = i == 0 || j == 0 || k == 0 || i == ne || j == ne || k == ne;
+    double y[3] = {0., 0., 0.};
+    if (!bnd) micro_apply(ske, sph, sx, n, i, j, k, y);
+#pragma unroll
+    for (int r = 0; r < 3; r++) {
+      const double rr = bnd ? 0. : -y[r], z = sd[3 * nd + r] * rr;
+      sr[3 * nd + r] = rr;
+      sp[3 * nd + r] = z;
+      sq[3 * nd + r] = 0.;
+      rz += rr * z;
+      zz += z * z;
+    }
+  }
+  micro_reduce2(rz, zz, sred);
+  const double norm0 = sqrt(zz);
+  int its = 0, conv = norm0 == 0.;  // n = 2 (no interior dof) or a load case the zero guess solves
+  double rel = 0.;
+  while (!conv && its < m.max_it) {
+    double pq = 0., dummy = 0.;
+    for (int nd = tid; nd < nn; nd += MICRO_TPB) {
+      const int i = nd % n, j = (nd / n) % n, k = nd / (n * n);
+      if (i == 0 || j == 0 || k == 0 || i == ne || j == ne || k == ne) continue;  // q stays 0
+      double y[3];
+      micro_apply(ske, sph, sp, n, i, j, k, y);
+#pragma unroll
+      for (int r = 0; r < 3; r++) {
+        sq[3 * nd + r] = y[r];
+        pq += sp[3 * nd + r] * y[r];
+      }
+    }
+    micro_reduce2(pq, dummy, sred);
+    if (!(pq > 0.)) break;  // no curvature left along p: reported as not converged
+    const double alpha = rz / pq;
+    double rz2 = 0., zz2 = 0.;
+    for (int d = tid; d < ndof; d += MICRO_TPB) {
+      sx[d] += alpha * sp[d];
+      const double rr = sr[d] - alpha * sq[d], z = sd[d] * rr;
+      sr[d] = rr;
+      rz2 += rr * z;
+      zz2 += z * z;
+    }
+    micro_reduce2(rz2, zz2, sred);
+    its++;
+    rel = sqrt(zz2) / norm0;
+    if (rel <= m.rtol) {
+      conv = 1;
+      break;
+    }
+    const double beta = rz2 / rz;
+    rz = rz2;
+    for (int d = tid; d < ndof; d += MICRO_TPB) sp[d] = sd[d] * sr[d] + beta * sp[d];
+    __syncthreads();
+  }
+  __syncthreads();
+  // volume average of the Gauss-point stresses (the cell's volume is 1)
+  double sg[6] = {0., 0., 0., 0., 0., 0.};
+  for (int e = tid; e < nel; e += MICRO_TPB) {
+    const int ei = e % ne, ej = (e / ne) % ne, ek = e / (ne * ne), ph = sph[e];
+    const double Ee = ph ? m.E[1] : m.E[0], nue = ph ? m.nu[1] : m.nu[0];
+#pragma unroll 1
+    for (int gp = 0; gp < 8; gp++) {
+      const double* dn = sdn + 24 * gp;
+      double G[3][3] = {{0., 0., 0.}, {0., 0., 0.}, {0., 0., 0.}};  // G[r][d] = d u_r / d x_d
+#pragma unroll 1
+      for (int a = 0; a < 8; a++) {
+        const int nb = (ei + (a & 1)) + n * ((ej + (a >> 1 & 1)) + n * (ek + (a >> 2)));
+#pragma unroll
+        for (int r = 0; r < 3; r++)
+#pragma unroll
+          for (int d = 0; d < 3; d++) G[r][d] += dn[3 * a + d] * sx[3 * nb + r];
+      }
+      const double eps[6] = {G[0][0], G[1][1], G[2][2], G[0][1] + G[1][0], G[0][2] + G[2][0], G[1][2] + G[2][1]};
+#pragma unroll
+      for (int k = 0; k < 6; k++) {
+        double s = 0.;
+#pragma unroll
+        for (int l = 0; l < 6; l++) s += micro_iso_C(Ee, nue, k, l) * eps[l];
+        sg[k] += s * detJ;
+      }
+    }
+  }
+  micro_reduce2(sg[0], sg[1], sred);
+  micro_reduce2(sg[2], sg[3], sred);
+  micro_reduce2(sg[4], sg[5], sred);
+  if (tid == 0) {
+    double* o = out + MICRO_OUT * lc;
+    for (int k = 0; k < 6; k++) o[k] = sg[k];
+    o[6] = (double)its;
+    o[7] = rel;
+    o[8] = (double)conv;
+  }
+}
+
 // One 3x3 block A(node g, node g+d) of the assembled matrix (MatSetValuesLocal(ADD) +
 // MatAssembly + MatZeroRowsColumns(diag = 1), src/assembly.c:106-112, src/bcs.c:341-347):
 // 0 + Ke_e1 + Ke_e2 + ... over the shared elements in ascending element order (the reference's
@@ -5520,7 +5825,7 @@ void launch_homogenize(Ctx& c) {
   if (c.mat.law == MCX_LAW_PLASTIC)
     hipLaunchKernelGGL(k_homogenize_plastic, dim3(nblk(ngp)), dim3(TPB), 0, c.stream, ngp, c.mat, c.eps, c.hist_old,
                        c.sig, c.ctan, c.hist_new, c.ftrial);
-  else if (c.mat.law == MCX_LAW_ELASTIC)
+  else if (c.mat.law == MCX_LAW_ELASTIC || c.mat.law == MCX_LAW_MICRO)  // micro: mat.C = C_hom, all 36 entries
     hipLaunchKernelGGL(k_homogenize_elastic, dim3(nblk(ngp)), dim3(TPB), 0, c.stream, ngp, c.mat, c.eps, c.sig);
 }
 
@@ -5528,12 +5833,21 @@ void launch_residual(Ctx& c) {
   hipLaunchKernelGGL(k_residual, dim3(nblk(c.g.nown)), dim3(TPB), 0, c.stream, c.g, c.sig, c.b, c.partials);
 }
 
-// every law but the isotropic elastic one hands over a per-GP tangent (ctan)
-static bool table_law(const Ctx& c) { return c.mat.law != MCX_LAW_ELASTIC; }
+// the plastic and external laws hand over a per-GP tangent (ctan); the elastic and micro laws have one
+static bool table_law(const Ctx& c) { return c.mat.law != MCX_LAW_ELASTIC && c.mat.law != MCX_LAW_MICRO; }
 // the element matrices matrix_block reads: per element (table laws) or the elastic law's one
 static const double* ke_src(const Ctx& c) { return table_law(c) ? c.Ke : c.ke_uni; }
 
-void launch_elastic_ke(Ctx& c) { hipLaunchKernelGGL(k_elastic_ke, dim3(1), dim3(64), 0, c.stream, c.g, c.mat, c.ke_uni); }
+void launch_elastic_ke(Ctx& c) {
+  if (c.mat.law == MCX_LAW_MICRO)
+    hipLaunchKernelGGL(k_micro_ke, dim3(1), dim3(64), 0, c.stream, c.g, c.mat, c.ke_uni);
+  else
+    hipLaunchKernelGGL(k_elastic_ke, dim3(1), dim3(64), 0, c.stream, c.g, c.mat, c.ke_uni);
+}
+
+void launch_micro_rve(Ctx& c, const MicroArgs& m) {
+  hipLaunchKernelGGL(k_micro_rve, dim3(6), dim3(MICRO_TPB), 0, c.stream, m, c.micro_out);
+}
 
 // element matrices of a per-GP-tangent law (k_element_ke), read by the gathers below
 void launch_element_ke(Ctx& c) {

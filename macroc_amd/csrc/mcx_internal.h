@@ -50,10 +50,31 @@ struct CgState {
 };
 
 struct Material {
-  int law;                 // MCX_LAW_ELASTIC | MCX_LAW_PLASTIC
+  int law;                 // MCX_LAW_ELASTIC | MCX_LAW_PLASTIC | MCX_LAW_EXTERNAL | MCX_LAW_MICRO
   double E, nu, Sy, Ka;
-  double C[36];            // isotropic elastic tangent (Voigt, engineering shear)
+  double C[36];            // isotropic elastic tangent (Voigt, engineering shear); -mat_law micro: C_hom
 };
+
+// -mat_law micro: the two-phase unit cell homogenised on the device (k_micro_rve)
+constexpr int MICRO_NMAX = 10;                                       // nodes per edge (micro_n) supported
+constexpr int MICRO_DOFS = 3 * MICRO_NMAX * MICRO_NMAX * MICRO_NMAX;  // LDS vectors are sized for it
+constexpr int MICRO_TPB = 512;
+constexpr int MICRO_OUT = 16;  // doubles a load case leaves: 6 average stresses, iterations, relative norm, converged
+struct MicroArgs {
+  int n, type;          // -micro_n, -micro_type
+  double E[2], nu[2];   // phase 0 = micro_mat_1, phase 1 = micro_mat_2
+  double rtol;          // stopping rule: |D^-1 r| <= rtol |D^-1 r_0|
+  int max_it;
+};
+// phase of micro element (i, j, k), indices 0 .. ne-1, in exact integer arithmetic: type 0 a
+// centred sphere of radius 0.5, type 1 a flat layer in y
+__host__ __device__ inline int micro_phase(int type, int ne, int i, int j, int k) {
+  if (type == 0) {
+    const int a = 2 * i + 1 - ne, b = 2 * j + 1 - ne, c = 2 * k + 1 - ne;
+    return a * a + b * b + c * c < ne * ne;
+  }
+  return 2 * j + 1 < ne;
+}
 
 struct HaloPlan {
   std::vector<int> nbr_rank;          // neighbour ranks (<= 26)
@@ -339,6 +360,16 @@ struct Ctx {
   int64_t device_bytes = 0;
   int64_t nnz_local = 0, nnz_global = 0;
 
+  // -mat_law micro: the cell's two materials and solver settings, the homogenised tangent (also in
+  // mat.C) with each load case's CG iterations and final relative norm; dirty = C_hom has to be
+  // (re)computed before it is next used (after init, mcx_material_set, a micro_* option)
+  MicroArgs micro{};
+  int micro_max_it = 0;      // option micro_max_it (0: 10 x interior dofs)
+  bool micro_dirty = true;
+  double* micro_out = nullptr;  // device [6][MICRO_OUT]
+  int micro_its[6] = {};
+  double micro_rnorm[6] = {};
+
   // external Gauss-point law (-mat_law external): host MicroPP-shaped callbacks or a device law
   mcx_micropp_api mpp{};
   bool has_mpp = false;
@@ -399,7 +430,8 @@ void launch_homogenize(Ctx& c);
 void launch_residual(Ctx& c);          // b + partial sums of b.b
 void launch_element_ke(Ctx& c);        // Ke of a per-GP-tangent law
 int launch_plain_ke(Ctx& c);           // plain elements, kref, the other elements' Ke (exception-node build)
-void launch_elastic_ke(Ctx& c);        // the elastic law's one element matrix (ke_uni)
+void launch_elastic_ke(Ctx& c);        // the elastic law's one element matrix (ke_uni); -mat_law micro: from C_hom
+void launch_micro_rve(Ctx& c, const MicroArgs& m);  // the six unit-strain solves of the micro cell -> micro_out
 void launch_gather_matrix(Ctx& c);
 void launch_gather_matrix_sym(Ctx& c);
 int build_split(Ctx& c, bool* exact);  // AIJ-split corrections from U (exact = usable)

@@ -164,6 +164,22 @@ static int run(int argc, char** argv) {
     return 2;
   }
 #endif
+  if (o.mat_law == MCX_LAW_MICRO) { /* src/init.c:196-213 with the micro cell solved on the device */
+    CHK(mcx_material_set(ctx, 0, o.micro_mat_1[0], o.micro_mat_1[1], o.micro_mat_1[2], o.micro_mat_1[3], 1));
+    CHK(mcx_material_set(ctx, 1, o.micro_mat_2[0], o.micro_mat_2[1], o.micro_mat_2[2], o.micro_mat_2[3], 1));
+    double chom[36], rn[6];
+    int cg_its[6];
+    CHK(mcx_micro_get_ctan(ctx, chom, cg_its, rn)); /* every rank solves its own, identical copy */
+    PRINTF("Material Values : \n");
+    PRINTF("id 0 : E = %e\tnu = %e\n", o.micro_mat_1[0], o.micro_mat_1[1]);
+    PRINTF("id 1 : E = %e\tnu = %e\n", o.micro_mat_2[0], o.micro_mat_2[1]);
+    PRINTF("Micro cell : type = %d (%s)\tn = %d\n", o.micro_type, o.micro_type == 0 ? "sphere" : "layer", o.micro_n);
+    PRINTF("C_hom : \n");
+    for (int k = 0; k < 6; k++)
+      PRINTF("%e\t%e\t%e\t%e\t%e\t%e\n", chom[k * 6], chom[k * 6 + 1], chom[k * 6 + 2], chom[k * 6 + 3],
+             chom[k * 6 + 4], chom[k * 6 + 5]);
+    PRINTF("Micro CG Its : %d %d %d %d %d %d\n\n", cg_its[0], cg_its[1], cg_its[2], cg_its[3], cg_its[4], cg_its[5]);
+  }
   PRINTF("Boundary Condition : %s\n", o.bc_type == MCX_BC_BENDING ? "BC_BENDING" : "BC_CIRCLE");
   PRINTF("Number of CPUs     : %d\n", in.nranks);
   PRINTF("Number of Elements : %ld\n", (long)((in.NX - 1) * (in.NY - 1) * (in.NZ - 1)));
