@@ -78,12 +78,13 @@ enum {
    lower triangle mirrored from it) */
 enum { MCX_MAT_AIJ = 0, MCX_MAT_SBAIJ = 1 };
 
-/* constitutive laws behind the Gauss-point callback (-mat_law elastic|plastic|external|micro):
+/* constitutive laws behind the Gauss-point callback (-mat_law elastic|plastic|external|micro|micro_nl):
    device isotropic elastic, device J2 plasticity (MicroPP material type 1), an external law
    registered through mcx_set_micropp / mcx_set_device_law / mcx_set_gp_stress+ctan, or the linear
    two-phase micro cell (-micro_n, -micro_type, -micro_mat_1/2) homogenised on the device: one
-   tangent C_hom, sigma = C_hom eps at every Gauss point (mcx_micro_get_ctan) */
-enum { MCX_LAW_ELASTIC = 0, MCX_LAW_PLASTIC = 1, MCX_LAW_EXTERNAL = 2, MCX_LAW_MICRO = 3 };
+   tangent C_hom, sigma = C_hom eps at every Gauss point (mcx_micro_get_ctan); micro_nl: the same
+   cell with J2-plastic phases, solved per Gauss point (below) */
+enum { MCX_LAW_ELASTIC = 0, MCX_LAW_PLASTIC = 1, MCX_LAW_EXTERNAL = 2, MCX_LAW_MICRO = 3, MCX_LAW_MICRO_NL = 4 };
 
 typedef struct {
   int64_t NX, NY, NZ;          /* -da_grid_x/y/z          (default 40 3 40, include/macroc.h:44-46) */
@@ -105,7 +106,7 @@ typedef struct {
   int device;                  /* HIP device of this rank (-1: rank % device count) */
   int ksp_monitor;             /* -ksp_monitor: keep the residual history */
   int mat_type;                /* -dm_mat_type aij|sbaij  (MCX_MAT_AIJ) */
-  int mat_law;                 /* -mat_law elastic|plastic|external|micro (MCX_LAW_ELASTIC; plastic = J2
+  int mat_law;                 /* -mat_law elastic|plastic|external|micro|micro_nl (MCX_LAW_ELASTIC; plastic = J2
                                   with micro_mat_1's Sy, Ka: MicroPP material type 1; micro = the
                                   two-phase micro cell homogenised on the device) */
   int mat_aij_split;           /* -mat_aij_split 0|1 (1): hold the AIJ matrix exactly as upper blocks +
@@ -227,7 +228,8 @@ int mcx_get_info(void* ctx, mcx_info* info);
 int mcx_comm_info(void* ctx, int* comm_ranks, int* comm_rank, int* device);
 
 /* Gauss-point constitutive model (micropp_C_material_set(id,E,nu,Sy,Ka,type)).  id 1 has to equal
-   id 0 except under -mat_law micro, where ids 0 and 1 are the micro cell's two phases */
+   id 0 except under -mat_law micro and micro_nl, where ids 0 and 1 are the micro cell's two phases
+   (micro_nl uses all four parameters of each) */
 int mcx_material_set(void* ctx, int id, double E, double nu, double Sy, double Ka, int type);
 
 /* ---- the MicroPP Gauss-point callback boundary (-mat_law external) ----
@@ -279,6 +281,9 @@ int mcx_set_device_law(void* ctx, const mcx_device_law* law);
 int mcx_set_gp_stress(void* ctx, const double* host /* [ngp][6] */);
 int mcx_set_gp_ctan(void* ctx, const double* host /* [ngp][36] */);
 int mcx_get_gp_strain(void* ctx, double* host /* [ngp][6] */);
+/* the tangents the last mcx_homogenize left, in mcx_get_gp_strain's index order (row major 6x6 per
+   Gauss point); any law with a tangent per Gauss point (plastic, external, micro_nl) */
+int mcx_get_gp_ctan(void* ctx, double* host /* [ngp][36] */);
 
 /* ---- the micro-scale cell (-mat_law micro) ----
  * The unit cube with micro_n nodes per edge (2 <= micro_n <= 10), ne = micro_n - 1 Q1 hexahedra per
@@ -301,6 +306,30 @@ int mcx_micro_get_ctan(void* ctx, double C[36], int its[6], double rnorm[6]);
 /* the elements' materials (0 / 1), x fastest: phase[i + ne*(j + ne*k)]; *n in: capacity, out:
    count ne^3 (phase may be NULL to query the count) */
 int mcx_micro_get_phase(void* ctx, unsigned char* phase, int64_t* n);
+
+/* ---- the non-linear micro-scale cell (-mat_law micro_nl) ----
+ * The cell above with both phases J2-plastic (E, nu, Sy, Ka of micro_mat_1 / micro_mat_2; small
+ * strain, linear isotropic hardening: the law of -mat_law plastic at every micro Gauss point, 7
+ * history doubles each).  A macro Gauss point with strain eps and committed history: boundary
+ * nodes carry u = E x (E_ab = eps_ab / 2 for shears), the interior solves R_i(u) = 0 by Newton from
+ * zero; every step is a Jacobi-CG on the consistent tangent stiffness ("micro_rtol",
+ * "micro_max_it").  Newton stops at |D^-1 R_i| <= "micro_nl_rtol" (1e-10) times its first value
+ * (D: the diagonal of K_T at the first iterate) and gives up after "micro_nl_max_it" (20)
+ * iterations.  sigma is the volume average of the micro stresses, the tangent the consistent
+ * homogenised one (six solves with the converged K_T frozen, symmetrised), f_trial the largest
+ * micro trial function.  A point whose elastic micro field (the superposition of the six
+ * unit-strain fields) yields nowhere, and which never did, takes the linear shortcut: sigma =
+ * C_hom eps, tangent C_hom, the bits of -mat_law micro.  Any other point takes a slot of the history
+ * pool for good; the pool is allocated at the first such point with "micro_nl_slots" slots (0 =
+ * default: what fits 2 GiB, at most the local Gauss points).  mcx_homogenize fails when the pool
+ * is too small or a cell does not converge; mcx_update_vars commits the histories.  micro_n = 2
+ * has no interior unknown: the one-element average of micro_mat_1's (micro_type 1) J2 law. */
+/* per Gauss point (mcx_get_gp_strain's order): path 0 = linear shortcut, 1 = solved; Newton
+   iterations, CG iterations (Newton steps and tangent solves together) and the final relative
+   Newton residual of the last mcx_homogenize.  Any pointer may be NULL. */
+int mcx_micro_nl_get_info(void* ctx, int* path, int* newton_its, int* cg_its, double* rnorm);
+/* slots in use, slots allocated (0 before the first non-linear point) and the bytes of one slot */
+int mcx_micro_nl_get_pool(void* ctx, int64_t* slots_used, int64_t* slots_allocated, int64_t* bytes_per_slot);
 
 double mcx_get_displacement(void* ctx, int time_s);
 int mcx_zero_u(void* ctx);                 /* VecZeroEntries(u)  src/init.c:103 */
@@ -363,7 +392,8 @@ int mcx_set_timing(void* ctx, int on);
 int mcx_get_timing(void* ctx, mcx_timing* t);
 int mcx_synchronize(void* ctx);
 /* tuning knobs ("spmv_subl": lines per sub-slab of the SpMV sweep, 0 = whole XCD slab; "micro_rtol",
-   "micro_max_it": the micro cell's CG, -mat_law micro) and a
+   "micro_max_it": the micro cell's CG, -mat_law micro; "micro_nl_rtol", "micro_nl_max_it", "micro_nl_slots":
+   -mat_law micro_nl) and a
    device-only SpMV timer (iters launches on the current search direction, HIP events) */
 int mcx_set_option(void* ctx, const char* name, double value);
 int mcx_time_spmv(void* ctx, int iters, double* avg_ms);

@@ -41,9 +41,10 @@ EXPORTS = [
     "mcx_set_timing", "mcx_get_timing", "mcx_synchronize", "mcx_set_option", "mcx_time_spmv",
     "mcx_set_micropp", "mcx_set_device_law", "mcx_set_gp_stress", "mcx_set_gp_ctan", "mcx_get_gp_strain",
     "mcx_micro_get_ctan", "mcx_micro_get_phase",
+    "mcx_get_gp_ctan", "mcx_micro_nl_get_info", "mcx_micro_nl_get_pool",
 ]
 
-LAWS = {"elastic": 0, "plastic": 1, "external": 2, "micro": 3}
+LAWS = {"elastic": 0, "plastic": 1, "external": 2, "micro": 3, "micro_nl": 4}
 
 
 class Opts(C.Structure):
@@ -182,7 +183,10 @@ def lib():
     L.mcx_time_spmv.argtypes = [vp, C.c_int, d]
     L.mcx_set_micropp.argtypes = [vp, C.POINTER(MicroppApi)]
     L.mcx_set_device_law.argtypes = [vp, C.POINTER(DeviceLaw)]
-    for fn in ("mcx_set_gp_stress", "mcx_set_gp_ctan", "mcx_get_gp_strain"):
+    ip = C.POINTER(C.c_int)
+    L.mcx_micro_nl_get_info.argtypes = [vp, ip, ip, ip, d]
+    L.mcx_micro_nl_get_pool.argtypes = [vp, i64, i64, i64]
+    for fn in ("mcx_set_gp_stress", "mcx_set_gp_ctan", "mcx_get_gp_strain", "mcx_get_gp_ctan"):
         getattr(L, fn).argtypes = [vp, d]
     L.mcx_micro_get_ctan.argtypes = [vp, d, C.POINTER(C.c_int), d]
     L.mcx_micro_get_phase.argtypes = [vp, C.POINTER(C.c_ubyte), i64]
@@ -430,6 +434,27 @@ class Macroc:
     def gp_strain(self):
         """strains of the callback box, [ngp][6] in gpi order."""
         return self._get("mcx_get_gp_strain", self.ngp * 6).reshape(-1, 6)
+
+    def gp_ctan(self):
+        """tangents of the last homogenize, [ngp][6][6] in gpi order (laws with a per-GP tangent)."""
+        return self._get("mcx_get_gp_ctan", self.ngp * 36).reshape(-1, 6, 6)
+
+    # ---- the non-linear micro-scale cell (-mat_law micro_nl)
+    def micro_nl_info(self):
+        """per Gauss point (gpi order): path (0 linear shortcut, 1 solved), Newton iterations, CG
+        iterations, final relative Newton residual; and the history pool: slots in use, slots
+        allocated (0 before the first non-linear point), bytes per slot."""
+        n = self.ngp
+        path, nit, cg = np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n, np.int32)
+        rn = np.zeros(n)
+        ip = C.POINTER(C.c_int)
+        _check(lib().mcx_micro_nl_get_info(self._ctx, path.ctypes.data_as(ip), nit.ctypes.data_as(ip),
+                                           cg.ctypes.data_as(ip), _dp(rn)), "mcx_micro_nl_get_info")
+        used, cap, per = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        _check(lib().mcx_micro_nl_get_pool(self._ctx, C.byref(used), C.byref(cap), C.byref(per)),
+               "mcx_micro_nl_get_pool")
+        return {"path": path, "newton_its": nit, "cg_its": cg, "rnorm": rn, "slots_used": used.value,
+                "slots": cap.value, "bytes_per_slot": per.value}
 
     # ---- the micro-scale cell (-mat_law micro)
     def micro_ctan(self):

@@ -70,7 +70,11 @@ static void elastic_C(double E, double nu, double C[36]) {
 
 // laws that hand over a tangent per Gauss point (ctan, element matrices per element); the elastic
 // law and the micro law (one homogenised tangent) have one tangent in the kernel argument
-static bool gp_tangent_law(int law) { return law == MCX_LAW_PLASTIC || law == MCX_LAW_EXTERNAL; }
+static bool gp_tangent_law(int law) {
+  return law == MCX_LAW_PLASTIC || law == MCX_LAW_EXTERNAL || law == MCX_LAW_MICRO_NL;
+}
+// laws built on the two-phase micro cell (C_hom, ensure_micro)
+static bool micro_law(int law) { return law == MCX_LAW_MICRO || law == MCX_LAW_MICRO_NL; }
 
 // phase timer: an event pair on the compute stream, recorded without any host wait (the
 // timed steps are not serialised by the instrumentation); mcx_get_timing resolves the last pair
@@ -95,7 +99,7 @@ static int free_ctx(Ctx* c) {
   if (c->comm_stream) (void)hipStreamSynchronize(c->comm_stream);
   if (c->x_stream) (void)hipStreamSynchronize(c->x_stream);
   if (c->f_stream) (void)hipStreamSynchronize(c->f_stream);
-  void* ptrs[] = {c->micro_out, c->hist_old, c->hist_new, c->ftrial, c->b, c->du, c->r, c->z, c->w, c->jix, c->jdd, c->V, c->U, c->D, c->d_mask, c->vi_idx, c->wd, c->vi_dict, c->vi_keys, c->vi_slot, c->vi_ctl, c->vi_bdict, c->eps, c->sig, c->ctan, c->Ke,
+  void* ptrs[] = {c->micro_out, c->mnl_ufield, c->mnl_conc, c->mnl_slot, c->mnl_list, c->mnl_cnt, c->mnl_its, c->mnl_rn, c->mnl_pool, c->hist_old, c->hist_new, c->ftrial, c->b, c->du, c->r, c->z, c->w, c->jix, c->jdd, c->V, c->U, c->D, c->d_mask, c->vi_idx, c->wd, c->vi_dict, c->vi_keys, c->vi_slot, c->vi_ctl, c->vi_bdict, c->eps, c->sig, c->ctan, c->Ke,
                   c->vib_keys, c->vib_ctl, c->vib_pos, c->ke_uni, c->xdone, c->esc_node, c->esc_res, c->esc_slot, c->elem_plain, c->cref, c->vi_xslot,
                   c->vi_xlist, c->vi_xcnt, c->vi_exc, c->st_coef, c->st_ids, c->st_slot, c->st_list, c->st_cnt, c->st_mask,
                   c->partials, c->red, c->red_loc, c->cg, c->hist, c->tmp, c->halo.d_send_idx,
@@ -222,7 +226,7 @@ static int init_ctx(Ctx& c, const mcx_opts* o, int rank, int nranks, const void*
   if (c.aij_split) MCX_HIP(hipMalloc(&c.d_mask, 16 * sizeof(unsigned)));
   MCX_HIP(hipHostMalloc((void**)&c.h_cg, sizeof(CgState) * 2, hipHostMallocDefault));
   std::memset(c.h_cg, 0, sizeof(CgState) * 2);
-  if (o->micro_n != 2 && o->mat_law != MCX_LAW_EXTERNAL && o->mat_law != MCX_LAW_MICRO && rank == 0)
+  if (o->micro_n != 2 && o->mat_law != MCX_LAW_EXTERNAL && !micro_law(o->mat_law) && rank == 0)
     std::fprintf(stderr,
                  "WARNING! -micro_n %d has no effect: the device Gauss-point laws have no micro-scale FE problem "
                  "(MicroPP's FE2 solver is out of scope); it sizes an external MicroPP (-mat_law external, "
@@ -234,7 +238,7 @@ static int init_ctx(Ctx& c, const mcx_opts* o, int rank, int nranks, const void*
   c.mat.Sy = o->micro_mat_1[2];
   c.mat.Ka = o->micro_mat_1[3];
   elastic_C(c.mat.E, c.mat.nu, c.mat.C);
-  if (o->mat_law == MCX_LAW_MICRO) {  // C_hom replaces mat.C at its first use (ensure_micro)
+  if (micro_law(o->mat_law)) {  // C_hom replaces mat.C at its first use (ensure_micro)
     if ((rc = dalloc(c, &c.micro_out, 6 * MICRO_OUT))) return rc;
     c.micro.n = o->micro_n;
     c.micro.type = o->micro_type;
@@ -244,6 +248,19 @@ static int init_ctx(Ctx& c, const mcx_opts* o, int rank, int nranks, const void*
     c.micro.nu[1] = o->micro_mat_2[1];
     c.micro.rtol = 1e-12;
     c.micro_dirty = true;
+  }
+  if (o->mat_law == MCX_LAW_MICRO_NL) {  // the pool itself waits for the first non-linear point
+    const int64_t ngp = 8 * E, mgp = 8 * (MICRO_NMAX - 1) * (MICRO_NMAX - 1) * (MICRO_NMAX - 1);
+    if ((rc = dalloc(c, &c.ftrial, ngp)) || (rc = dalloc(c, &c.mnl_ufield, 6 * MICRO_DOFS)) ||
+        (rc = dalloc(c, &c.mnl_conc, MNL_CONC * mgp)) || (rc = dalloc(c, &c.mnl_slot, ngp)) ||
+        (rc = dalloc(c, &c.mnl_list, ngp)) || (rc = dalloc(c, &c.mnl_cnt, 4)) ||
+        (rc = dalloc(c, &c.mnl_its, 3 * ngp)) || (rc = dalloc(c, &c.mnl_rn, ngp)))
+      return rc;
+    MCX_HIP(hipMemsetAsync(c.mnl_slot, 0xff, sizeof(int) * (ngp > 0 ? ngp : 1), c.stream));  // -1: no slot
+    c.mnl_Sy[0] = o->micro_mat_1[2];
+    c.mnl_Ka[0] = o->micro_mat_1[3];
+    c.mnl_Sy[1] = o->micro_mat_2[2];
+    c.mnl_Ka[1] = o->micro_mat_2[3];
   }
   c.nnz_local = count_nnz_rows(c, g.xs, g.ys, g.zs, g.nx, g.ny, g.nz);
   c.nnz_global = count_nnz_rows(c, 0, 0, 0, o->NX, o->NY, o->NZ);
@@ -468,13 +485,14 @@ int mcx_parse_args(mcx_opts* o, int argc, const char* const* argv) try {
     if (!std::strcmp(k, "-mat_ignore_lower_triangular")) continue;
     if (!std::strcmp(k, "-mat_law")) {
       if (!v || (std::strcmp(v, "elastic") && std::strcmp(v, "plastic") && std::strcmp(v, "external") &&
-                 std::strcmp(v, "micro"))) {
-        set_error(std::string("-mat_law: elastic, plastic, external or micro, got ") + (v ? v : "(none)"));
+                 std::strcmp(v, "micro") && std::strcmp(v, "micro_nl"))) {
+        set_error(std::string("-mat_law: micro_nl, elastic, plastic, external or micro, got ") + (v ? v : "(none)"));
         return 2;
       }
       o->mat_law = !std::strcmp(v, "plastic") ? MCX_LAW_PLASTIC
                    : !std::strcmp(v, "external") ? MCX_LAW_EXTERNAL
                    : !std::strcmp(v, "micro")    ? MCX_LAW_MICRO
+                   : !std::strcmp(v, "micro_nl") ? MCX_LAW_MICRO_NL
                                                  : MCX_LAW_ELASTIC;
       a++;
       continue;
@@ -697,7 +715,7 @@ int mcx_material_set(void* ctx, int id, double E, double nu, double Sy, double K
   (void)Sy;
   (void)Ka;
   (void)type;
-  if (c.mat.law == MCX_LAW_MICRO) {  // the micro cell's two phases; Sy, Ka unused (linear micro problem)
+  if (micro_law(c.mat.law)) {  // the micro cell's two phases; Sy, Ka: -mat_law micro_nl only
     if (id != 0 && id != 1) {
       set_error("mcx_material_set: -mat_law micro has materials 0 and 1");
       return 3;
@@ -710,6 +728,8 @@ int mcx_material_set(void* ctx, int id, double E, double nu, double Sy, double K
     }
     c.micro.E[id] = E;
     c.micro.nu[id] = nu;
+    c.mnl_Sy[id] = Sy;
+    c.mnl_Ka[id] = Ka;
     c.micro_dirty = true;
     return 0;
   }
@@ -765,8 +785,22 @@ int mcx_set_strains(void* ctx) try {
 // -mat_law micro: C_hom of the two-phase cell into mat.C when it is not current: six
 // unit-strain solves in one launch (k_micro_rve), column l = block l's average stress, then
 // C_hom = (C + C^T) / 2 on the host (exactly symmetric; the same bits in every context)
+static MicroNlArgs mnl_args(const Ctx& c) {
+  MicroNlArgs a{};
+  a.m = c.micro;
+  const int interior = 3 * (a.m.n - 2) * (a.m.n - 2) * (a.m.n - 2);
+  a.m.max_it = c.micro_max_it > 0 ? c.micro_max_it : 10 * interior;
+  for (int p = 0; p < 2; p++) {
+    a.Sy[p] = c.mnl_Sy[p];
+    a.Ka[p] = c.mnl_Ka[p];
+  }
+  a.nl_rtol = c.mnl_rtol;
+  a.nl_max_it = c.mnl_max_it;
+  return a;
+}
+
 static int ensure_micro(Ctx& c) {
-  if (c.mat.law != MCX_LAW_MICRO || !c.micro_dirty) return 0;
+  if (!micro_law(c.mat.law) || !c.micro_dirty) return 0;
   MicroArgs m = c.micro;
   if (m.n < 2 || m.n > MICRO_NMAX) {
     set_error("-mat_law micro: -micro_n " + std::to_string(m.n) + " outside the supported range 2 <= micro_n <= " +
@@ -804,7 +838,88 @@ static int ensure_micro(Ctx& c) {
   }
   for (int k = 0; k < 6; k++)
     for (int l = 0; l < 6; l++) c.mat.C[k * 6 + l] = 0.5 * (Cc[k * 6 + l] + Cc[l * 6 + k]);
+  if (c.mat.law == MCX_LAW_MICRO_NL) {  // the linear test's strain concentration tensors from the six fields
+    launch_mnl_conc(c, mnl_args(c));
+    MCX_HIP(hipGetLastError());
+  }
   c.micro_dirty = false;
+  return 0;
+}
+
+// -mat_law micro_nl: the linear test of the points without a slot, slots for those
+// that fail it, then one non-linear cell solve per slotted point
+static int64_t mnl_slot_bytes(const Ctx& c) {
+  const int64_t ne = c.micro.n - 1;
+  return (int64_t)sizeof(double) * MNL_WS * 8 * ne * ne * ne;
+}
+
+static int micro_nl_homogenize(Ctx& c) {
+  if (int rc = ensure_micro(c)) return rc;
+  const MicroNlArgs a = mnl_args(c);
+  const int64_t ngp = 8 * c.g.nelem, bytes = mnl_slot_bytes(c);
+  int64_t want = c.mnl_slots_opt;
+  if (want <= 0) want = std::max<int64_t>(1, std::min<int64_t>(ngp, ((int64_t)2 << 30) / bytes));
+  if (c.mnl_pool && want != c.mnl_cap) {  // micro_nl_slots changed with slots in use: move them
+    if (want < c.mnl_used) {
+      set_error("micro_nl_slots " + std::to_string(want) + " is below the " + std::to_string(c.mnl_used) +
+                " slots in use");
+      return 34;
+    }
+    double* p = nullptr;
+    MCX_HIP(hipMalloc((void**)&p, (size_t)(want * bytes)));
+    MCX_HIP(hipMemsetAsync(p, 0, (size_t)(want * bytes), c.stream));
+    MCX_HIP(hipMemcpyAsync(p, c.mnl_pool, (size_t)(c.mnl_used * bytes), hipMemcpyDeviceToDevice, c.stream));
+    MCX_HIP(hipStreamSynchronize(c.stream));
+    MCX_HIP(hipFree(c.mnl_pool));
+    c.device_bytes += (want - c.mnl_cap) * bytes;
+    c.mnl_pool = p;
+  }
+  c.mnl_cap = want;
+  launch_mnl_linear(c, a);
+  MCX_HIP(hipGetLastError());
+  int h[4];
+  MCX_HIP(hipMemcpyAsync(h, c.mnl_cnt, sizeof(h), hipMemcpyDeviceToHost, c.stream));
+  MCX_HIP(hipStreamSynchronize(c.stream));
+  if (h[1] < 0) {
+    char buf[320];
+    std::snprintf(buf, sizeof(buf),
+                  "-mat_law micro_nl: the history pool is too small: micro_nl_slots %lld, %lld slots in use and %d more "
+                  "Gauss points left the linear range (%lld needed; %lld bytes per slot)",
+                  (long long)c.mnl_cap, (long long)c.mnl_used, h[0], (long long)(c.mnl_used + h[0]), (long long)bytes);
+    set_error(buf);
+    return 34;
+  }
+  if (h[1] == 0) return 0;
+  if (!c.mnl_pool) {
+    MCX_HIP(hipMalloc((void**)&c.mnl_pool, (size_t)(c.mnl_cap * bytes)));
+    MCX_HIP(hipMemsetAsync(c.mnl_pool, 0, (size_t)(c.mnl_cap * bytes), c.stream));
+    c.device_bytes += c.mnl_cap * bytes;
+  }
+  c.mnl_used += h[0];
+  launch_mnl_solve(c, a, h[1]);
+  MCX_HIP(hipGetLastError());
+  MCX_HIP(hipMemcpyAsync(h, c.mnl_cnt, sizeof(h), hipMemcpyDeviceToHost, c.stream));
+  MCX_HIP(hipStreamSynchronize(c.stream));
+  if (h[2] > 0) {  // nothing unconverged is used: name the count and the worst point
+    std::vector<int> its((size_t)3 * ngp);
+    std::vector<double> rn((size_t)ngp);
+    MCX_HIP(hipMemcpy(its.data(), c.mnl_its, sizeof(int) * its.size(), hipMemcpyDeviceToHost));
+    MCX_HIP(hipMemcpy(rn.data(), c.mnl_rn, sizeof(double) * rn.size(), hipMemcpyDeviceToHost));
+    int64_t worst = -1;
+    for (int64_t q = 0; q < ngp; q++)
+      if (its[2 * ngp + q] && (worst < 0 || !(rn[q] <= rn[worst]))) worst = q;
+    const int64_t E = c.g.nelem;
+    char buf[400];
+    std::snprintf(buf, sizeof(buf),
+                  "-mat_law micro_nl: %d of %d micro cells did not converge; worst: Gauss point %lld (%s): %d Newton "
+                  "iterations (micro_nl_max_it %d), %d CG iterations (micro_max_it %d), relative residual %.3e > "
+                  "micro_nl_rtol %.3e",
+                  h[2], h[1], (long long)((worst % E) * 8 + worst / E),
+                  its[2 * ngp + worst] == 1 ? "Newton gave up" : "the inner CG did not converge", its[worst],
+                  a.nl_max_it, its[ngp + worst], a.m.max_it, rn[worst], a.nl_rtol);
+    set_error(buf);
+    return 35;
+  }
   return 0;
 }
 
@@ -859,6 +974,7 @@ int mcx_homogenize(void* ctx) try {
   CTX(ctx);
   PhaseTimer t(c, PH_HOMOG);
   if (c.mat.law == MCX_LAW_EXTERNAL) return external_homogenize(c);
+  if (c.mat.law == MCX_LAW_MICRO_NL) return micro_nl_homogenize(c);
   if (int rc = ensure_micro(c)) return rc;
   launch_homogenize(c);
   MCX_HIP(hipGetLastError());
@@ -943,11 +1059,69 @@ int mcx_get_gp_strain(void* ctx, double* host) try {
   return 0;
 } MCX_CATCH
 
+int mcx_get_gp_ctan(void* ctx, double* host) try {
+  MCX_ENTRY();
+  GUARD(ctx);
+  CTX(ctx);
+  if (!c.ctan) {
+    set_error("mcx_get_gp_ctan: this -mat_law has no tangent per Gauss point (plastic, external, micro_nl have)");
+    return 7;
+  }
+  const int64_t E = c.g.nelem, ngp = 8 * E;
+  std::vector<double> soa((size_t)ngp * 36);
+  MCX_HIP(hipMemcpyAsync(soa.data(), c.ctan, sizeof(double) * soa.size(), hipMemcpyDeviceToHost, c.stream));
+  MCX_HIP(hipStreamSynchronize(c.stream));
+  for (int64_t e = 0; e < E; e++)
+    for (int gp = 0; gp < 8; gp++)
+      for (int k = 0; k < 36; k++) host[(e * 8 + gp) * 36 + k] = soa[(size_t)k * ngp + gp * E + e];
+  return 0;
+} MCX_CATCH
+
+static int need_micro_nl(Ctx& c, const char* fn) {
+  if (c.mat.law == MCX_LAW_MICRO_NL) return 0;
+  set_error(std::string(fn) + ": the context was created without -mat_law micro_nl");
+  return 7;
+}
+
+int mcx_micro_nl_get_info(void* ctx, int* path, int* newton_its, int* cg_its, double* rnorm) try {
+  MCX_ENTRY();
+  GUARD(ctx);
+  CTX(ctx);
+  if (int rc = need_micro_nl(c, "mcx_micro_nl_get_info")) return rc;
+  const int64_t E = c.g.nelem, ngp = 8 * E;
+  std::vector<int> slot((size_t)ngp), its((size_t)3 * ngp);
+  std::vector<double> rn((size_t)ngp);
+  MCX_HIP(hipMemcpyAsync(slot.data(), c.mnl_slot, sizeof(int) * slot.size(), hipMemcpyDeviceToHost, c.stream));
+  MCX_HIP(hipMemcpyAsync(its.data(), c.mnl_its, sizeof(int) * its.size(), hipMemcpyDeviceToHost, c.stream));
+  MCX_HIP(hipMemcpyAsync(rn.data(), c.mnl_rn, sizeof(double) * rn.size(), hipMemcpyDeviceToHost, c.stream));
+  MCX_HIP(hipStreamSynchronize(c.stream));
+  for (int64_t e = 0; e < E; e++)
+    for (int gp = 0; gp < 8; gp++) {
+      const int64_t q = gp * E + e, i = e * 8 + gp;
+      if (path) path[i] = slot[q] >= 0;
+      if (newton_its) newton_its[i] = its[q];
+      if (cg_its) cg_its[i] = its[ngp + q];
+      if (rnorm) rnorm[i] = rn[q];
+    }
+  return 0;
+} MCX_CATCH
+
+int mcx_micro_nl_get_pool(void* ctx, int64_t* slots_used, int64_t* slots_allocated, int64_t* bytes_per_slot) try {
+  MCX_ENTRY();
+  GUARD(ctx);
+  CTX(ctx);
+  if (int rc = need_micro_nl(c, "mcx_micro_nl_get_pool")) return rc;
+  if (slots_used) *slots_used = c.mnl_used;
+  if (slots_allocated) *slots_allocated = c.mnl_pool ? c.mnl_cap : 0;
+  if (bytes_per_slot) *bytes_per_slot = c.micro.n >= 2 && c.micro.n <= MICRO_NMAX ? mnl_slot_bytes(c) : 0;
+  return 0;
+} MCX_CATCH
+
 int mcx_micro_get_ctan(void* ctx, double* C, int* its, double* rnorm) try {
   MCX_ENTRY();
   GUARD(ctx);
   CTX(ctx);
-  if (c.mat.law != MCX_LAW_MICRO) {
+  if (!micro_law(c.mat.law)) {
     set_error("mcx_micro_get_ctan: the context was created without -mat_law micro");
     return 7;
   }
@@ -964,7 +1138,7 @@ int mcx_micro_get_phase(void* ctx, unsigned char* phase, int64_t* n) try {
   MCX_ENTRY();
   GUARD(ctx);
   CTX(ctx);
-  if (c.mat.law != MCX_LAW_MICRO) {
+  if (!micro_law(c.mat.law)) {
     set_error("mcx_micro_get_phase: the context was created without -mat_law micro");
     return 7;
   }
@@ -1144,6 +1318,10 @@ int mcx_update_vars(void* ctx) try {
   GUARD(ctx);
   CTX(ctx);
   if (c.hist_old) std::swap(c.hist_old, c.hist_new);
+  if (c.mat.law == MCX_LAW_MICRO_NL && c.mnl_pool) {
+    launch_mnl_commit(c, mnl_args(c));
+    MCX_HIP(hipGetLastError());
+  }
   if (c.has_mpp && c.mpp.update_vars) c.mpp.update_vars();
   if (c.has_dlaw && c.dlaw.update_vars) {
     MCX_HIP(hipStreamSynchronize(c.stream));
@@ -1660,6 +1838,30 @@ int mcx_set_option(void* ctx, const char* name, double value) try {
     }
     c.micro.rtol = value;
     c.micro_dirty = true;
+    return 0;
+  }
+  if (!std::strcmp(name, "micro_nl_rtol")) {  // -mat_law micro_nl: the cell's Newton stopping rule
+    if (!(value > 0.)) {
+      set_error("micro_nl_rtol: > 0");
+      return 1;
+    }
+    c.mnl_rtol = value;
+    return 0;
+  }
+  if (!std::strcmp(name, "micro_nl_max_it")) {
+    if (!(value >= 1.)) {
+      set_error("micro_nl_max_it: >= 1");
+      return 1;
+    }
+    c.mnl_max_it = (int)value;
+    return 0;
+  }
+  if (!std::strcmp(name, "micro_nl_slots")) {  // 0: what fits 2 GiB, at most the local Gauss points
+    if (!(value >= 0.)) {
+      set_error("micro_nl_slots: >= 0");
+      return 1;
+    }
+    c.mnl_slots_opt = (int64_t)value;
     return 0;
   }
   if (!std::strcmp(name, "micro_max_it")) {  // 0: 10 x the interior dofs

@@ -302,21 +302,13 @@ __device__ __forceinline__ void j2_elastic_tangent(double G, double K, double (&
 }
 
 // small-strain J2 plasticity with linear isotropic hardening (MicroPP material type 1: E, nu,
-// Sy, Ka), radial return + consistent tangent; same operation order as orc_j2_point (oracle).
-__global__ void k_homogenize_plastic(int64_t ngp, Material mat, const double* __restrict__ eps,
-                                     const double* __restrict__ hold, double* __restrict__ sig,
-                                     double* __restrict__ ctan, double* __restrict__ hnew,
-                                     double* __restrict__ ftrial) {
-  int64_t q = (int64_t)blockIdx.x * TPB + threadIdx.x;
-  if (q >= ngp) return;
-  const double Sy = mat.Sy, Ka = mat.Ka;
-  double G, K;
-  j2_moduli(mat, G, K);
-  double e[6], h[7];
-#pragma unroll
-  for (int l = 0; l < 6; l++) e[l] = eps[l * ngp + q];
-#pragma unroll
-  for (int l = 0; l < 7; l++) h[l] = hold[l * ngp + q];
+// Sy, Ka), radial return; same operation order as orc_j2_point (oracle).  One point: strain e
+// (Voigt, engineering shear) and history h (plastic strain in tensor components, then alpha) give
+// the trial function f (returned), the stress s, the new history hn and what the consistent tangent
+// needs: theta, theta-bar and the flow direction n (1, 0, 0 on the elastic branch f <= 0).
+__device__ __forceinline__ double j2_point(double G, double K, double Sy, double Ka, const double (&e)[6],
+                                           const double (&h)[7], double (&s)[6], double (&hn)[7], double& theta,
+                                           double& thetab, double (&n)[6]) {
   const double tr = e[0] + e[1] + e[2];
   double dev[6], st[6];
 #pragma unroll
@@ -330,19 +322,19 @@ __global__ void k_homogenize_plastic(int64_t ngp, Material mat, const double* __
   const double snorm = sqrt(nrm2);
   const double alpha = h[6];
   const double f = snorm - sqrt(2. / 3.) * (Sy + Ka * alpha);
-  ftrial[q] = f;
-  double C[36], s[6];
-  j2_elastic_tangent(G, K, C);
   if (f <= 0.) {
 #pragma unroll
     for (int i = 0; i < 3; i++) s[i] = K * tr + st[i];
 #pragma unroll
     for (int i = 3; i < 6; i++) s[i] = st[i];
 #pragma unroll
-    for (int i = 0; i < 7; i++) hnew[i * ngp + q] = h[i];
+    for (int i = 0; i < 7; i++) hn[i] = h[i];
+#pragma unroll
+    for (int i = 0; i < 6; i++) n[i] = 0.;
+    theta = 1.;
+    thetab = 0.;
   } else {
     const double dg = f / (2. * G + 2. / 3. * Ka);
-    double n[6];
 #pragma unroll
     for (int i = 0; i < 6; i++) n[i] = st[i] / snorm;
 #pragma unroll
@@ -350,21 +342,49 @@ __global__ void k_homogenize_plastic(int64_t ngp, Material mat, const double* __
 #pragma unroll
     for (int i = 3; i < 6; i++) s[i] = st[i] - 2. * G * dg * n[i];
 #pragma unroll
-    for (int i = 0; i < 6; i++) hnew[i * ngp + q] = h[i] + dg * n[i];
-    hnew[6 * ngp + q] = alpha + sqrt(2. / 3.) * dg;
-    const double theta = 1. - 2. * G * dg / snorm;
-    const double thetab = 1. / (1. + Ka / (3. * G)) - (1. - theta);
-#pragma unroll
-    for (int a = 0; a < 3; a++)
-#pragma unroll
-      for (int b = 0; b < 3; b++) C[a * 6 + b] = K + 2. * G * theta * ((a == b ? 1. : 0.) - 1. / 3.);
-#pragma unroll
-    for (int a = 3; a < 6; a++) C[a * 6 + a] = G * theta;
-#pragma unroll
-    for (int a = 0; a < 6; a++)
-#pragma unroll
-      for (int b = 0; b < 6; b++) C[a * 6 + b] = C[a * 6 + b] - 2. * G * thetab * n[a] * n[b];
+    for (int i = 0; i < 6; i++) hn[i] = h[i] + dg * n[i];
+    hn[6] = alpha + sqrt(2. / 3.) * dg;
+    theta = 1. - 2. * G * dg / snorm;
+    thetab = 1. / (1. + Ka / (3. * G)) - (1. - theta);
   }
+  return f;
+}
+
+// the consistent tangent of a yielding point (f > 0) from theta, theta-bar and n
+__device__ __forceinline__ void j2_plastic_tangent(double G, double K, double theta, double thetab,
+                                                   const double (&n)[6], double (&C)[36]) {
+#pragma unroll
+  for (int a = 0; a < 3; a++)
+#pragma unroll
+    for (int b = 0; b < 3; b++) C[a * 6 + b] = K + 2. * G * theta * ((a == b ? 1. : 0.) - 1. / 3.);
+#pragma unroll
+  for (int a = 3; a < 6; a++) C[a * 6 + a] = G * theta;
+#pragma unroll
+  for (int a = 0; a < 6; a++)
+#pragma unroll
+    for (int b = 0; b < 6; b++) C[a * 6 + b] = C[a * 6 + b] - 2. * G * thetab * n[a] * n[b];
+}
+
+__global__ void k_homogenize_plastic(int64_t ngp, Material mat, const double* __restrict__ eps,
+                                     const double* __restrict__ hold, double* __restrict__ sig,
+                                     double* __restrict__ ctan, double* __restrict__ hnew,
+                                     double* __restrict__ ftrial) {
+  int64_t q = (int64_t)blockIdx.x * TPB + threadIdx.x;
+  if (q >= ngp) return;
+  double G, K;
+  j2_moduli(mat, G, K);
+  double e[6], h[7], s[6], hn[7], n[6], theta, thetab;
+#pragma unroll
+  for (int l = 0; l < 6; l++) e[l] = eps[l * ngp + q];
+#pragma unroll
+  for (int l = 0; l < 7; l++) h[l] = hold[l * ngp + q];
+  const double f = j2_point(G, K, mat.Sy, mat.Ka, e, h, s, hn, theta, thetab, n);
+  ftrial[q] = f;
+  double C[36];
+  j2_elastic_tangent(G, K, C);
+  if (!(f <= 0.)) j2_plastic_tangent(G, K, theta, thetab, n, C);
+#pragma unroll
+  for (int i = 0; i < 7; i++) hnew[i * ngp + q] = hn[i];
 #pragma unroll
   for (int k2 = 0; k2 < 6; k2++) sig[k2 * ngp + q] = s[k2];
 #pragma unroll
@@ -688,7 +708,8 @@ __device__ __forceinline__ void micro_apply(const double* __restrict__ ske, cons
   }
 }
 
-__global__ __launch_bounds__(MICRO_TPB) void k_micro_rve(MicroArgs m, double* __restrict__ out) {
+__global__ __launch_bounds__(MICRO_TPB) void k_micro_rve(MicroArgs m, double* __restrict__ out,
+                                                          double* __restrict__ ufield) {
   __shared__ double sx[MICRO_DOFS], sr[MICRO_DOFS], sp[MICRO_DOFS], sq[MICRO_DOFS], sd[MICRO_DOFS];
   __shared__ double ske[2 * 576];
   __shared__ double sdn[8 * 24];  // [gp][a][d] physical shape-function gradients
@@ -861,6 +882,536 @@ __global__ __launch_bounds__(MICRO_TPB) void k_micro_rve(MicroArgs m, double* __
     o[7] = rel;
     o[8] = (double)conv;
   }
+  // -mat_law micro_nl keeps the unit-strain solution (the linear test superposes the six fields)
+  if (ufield)
+    for (int d = tid; d < ndof; d += MICRO_TPB) ufield[(size_t)lc * ndof + d] = sx[d];
+}
+
+// ---------------------------------------------------------------------------- non-linear micro cell
+// -mat_law micro_nl: the cell of k_micro_rve with J2-plastic phases (j2_point),
+// solved per macro Gauss point.  Three steps per mcx_homogenize:
+//   k_mnl_linear   every point without a slot: the elastic micro field is the superposition of the
+//                  six unit-strain fields (strain concentration tensors, k_mnl_conc); if no micro
+//                  point yields on it the point gets sigma = C_hom eps, ctan = C_hom (the bits of
+//                  -mat_law micro), else it is flagged
+//   k_mnl_compact  one block: flagged points get the next slots in ascending point order, and
+//                  every slotted point enters the list of points to solve, ascending
+//   k_mnl_solve    one workgroup per listed point: Newton on the interior dofs, each step a
+//                  Jacobi-CG in LDS, then the six frozen-tangent solves of the consistent tangent
+// A point's results depend on its strain and its committed history only: no arithmetic involves
+// the slot number or the block index.
+
+// the shape-function gradient table [gp][a][d] of the micro element (as k_micro_rve builds it)
+__device__ __forceinline__ double mnl_dn(int t, int ne) {
+  const int gp = t / 24, a = (t % 24) / 3, d = t % 3;
+  const double gq = 0.57735026918962576451;
+  double v = 0.125 * (2. * (double)ne);
+  for (int q = 0; q < 3; q++) {
+    const double sa = (a >> q & 1) ? 1. : -1., xi = (gp >> q & 1) ? gq : -gq;
+    v *= (q == d) ? sa : (1. + sa * xi);
+  }
+  return v;
+}
+
+// strain (Voigt, engineering shear) of micro element (ei, ej, ek) at the Gauss point whose
+// gradients are dn[a][d], from the nodal field v
+__device__ __forceinline__ void mnl_strain(const double* __restrict__ dn, const double* __restrict__ v, int n, int ei,
+                                           int ej, int ek, double (&eps)[6]) {
+  double G[3][3] = {{0., 0., 0.}, {0., 0., 0.}, {0., 0., 0.}};  // G[r][d] = d u_r / d x_d
+#pragma unroll 1
+  for (int a = 0; a < 8; a++) {
+    const int nb = (ei + (a & 1)) + n * ((ej + (a >> 1 & 1)) + n * (ek + (a >> 2)));
+#pragma unroll
+    for (int r = 0; r < 3; r++)
+#pragma unroll
+      for (int d = 0; d < 3; d++) G[r][d] += dn[3 * a + d] * v[3 * nb + r];
+  }
+  eps[0] = G[0][0];
+  eps[1] = G[1][1];
+  eps[2] = G[2][2];
+  eps[3] = G[0][1] + G[1][0];
+  eps[4] = G[0][2] + G[2][0];
+  eps[5] = G[1][2] + G[2][1];
+}
+
+// s = C e for the J2 tangent held as theta, theta-bar and n (elastic point: 1, 0, 0)
+__device__ __forceinline__ void mnl_Cmul(double G, double K, double th, double thb, const double (&nv)[6],
+                                         const double (&e)[6], double (&s)[6]) {
+  const double tr = e[0] + e[1] + e[2];
+  double t = 0.;
+#pragma unroll
+  for (int b = 0; b < 6; b++) t += nv[b] * e[b];
+  const double c = 2. * G * thb * t;
+#pragma unroll
+  for (int a = 0; a < 3; a++) s[a] = K * tr + 2. * G * th * (e[a] - tr / 3.) - c * nv[a];
+#pragma unroll
+  for (int a = 3; a < 6; a++) s[a] = G * th * e[a] - c * nv[a];
+}
+
+// per micro Gauss point: the strain concentration tensor A (eps_micro = A eps_macro on the
+// elastic field), 2G and sqrt(2/3) Sy of its phase
+__global__ __launch_bounds__(256) void k_mnl_conc(MicroNlArgs a, const double* __restrict__ ufield,
+                                                  double* __restrict__ conc) {
+  __shared__ double sdn[8 * 24];
+  const int n = a.m.n, ne = n - 1, ndof = 3 * n * n * n, nmgp = 8 * ne * ne * ne;
+  if (threadIdx.x < 8 * 24) sdn[threadIdx.x] = mnl_dn(threadIdx.x, ne);
+  __syncthreads();
+  const int mg = blockIdx.x * 256 + threadIdx.x;
+  if (mg >= nmgp) return;
+  const int e = mg >> 3, gp = mg & 7, ei = e % ne, ej = (e / ne) % ne, ek = e / (ne * ne);
+  const int ph = micro_phase(a.m.type, ne, ei, ej, ek);
+#pragma unroll 1
+  for (int l = 0; l < 6; l++) {
+    double eps[6];
+    mnl_strain(sdn + 24 * gp, ufield + (size_t)l * ndof, n, ei, ej, ek, eps);
+#pragma unroll
+    for (int k = 0; k < 6; k++) conc[(size_t)(k * 6 + l) * nmgp + mg] = eps[k];
+  }
+  const double G = a.m.E[ph] / (2. * (1. + a.m.nu[ph]));
+  conc[(size_t)36 * nmgp + mg] = 2. * G;
+  conc[(size_t)37 * nmgp + mg] = sqrt(2. / 3.) * a.Sy[ph];
+}
+
+// the linear test of every point without a slot; slot -2 flags a point for k_mnl_compact
+__global__ __launch_bounds__(TPB) void k_mnl_linear(int64_t ngp, Material mat, int nmgp,
+                                                    const double* __restrict__ conc, const double* __restrict__ eps,
+                                                    int* __restrict__ slot, double* __restrict__ sig,
+                                                    double* __restrict__ ctan, double* __restrict__ ftrial,
+                                                    int* __restrict__ its, double* __restrict__ rn) {
+  const int64_t q = (int64_t)blockIdx.x * TPB + threadIdx.x;
+  if (q >= ngp || slot[q] >= 0) return;
+  double e[6];
+#pragma unroll
+  for (int l = 0; l < 6; l++) e[l] = eps[l * ngp + q];
+  double fmax = -1e300;
+#pragma unroll 1
+  for (int mg = 0; mg < nmgp; mg++) {
+    double em[6];
+#pragma unroll
+    for (int k = 0; k < 6; k++) {
+      double s = 0.;
+#pragma unroll
+      for (int l = 0; l < 6; l++) s += conc[(size_t)(k * 6 + l) * nmgp + mg] * e[l];
+      em[k] = s;
+    }
+    const double g2 = conc[(size_t)36 * nmgp + mg], sy = conc[(size_t)37 * nmgp + mg];
+    const double tr = em[0] + em[1] + em[2];
+    double st[6];
+#pragma unroll
+    for (int i = 0; i < 3; i++) st[i] = g2 * (em[i] - tr / 3.);
+#pragma unroll
+    for (int i = 3; i < 6; i++) st[i] = g2 * (em[i] / 2.);
+    double nrm2 = st[0] * st[0] + st[1] * st[1] + st[2] * st[2];
+    nrm2 = nrm2 + 2. * (st[3] * st[3] + st[4] * st[4] + st[5] * st[5]);
+    const double f = sqrt(nrm2) - sy;
+    fmax = f > fmax ? f : fmax;
+  }
+  if (fmax > 0.) {
+    slot[q] = -2;
+    return;
+  }
+#pragma unroll
+  for (int k = 0; k < 6; k++) {  // k_homogenize_elastic's arithmetic: the bits of -mat_law micro
+    double s = 0.;
+#pragma unroll
+    for (int l = 0; l < 6; l++) s += mat.C[k * 6 + l] * e[l];
+    sig[k * ngp + q] = s;
+  }
+#pragma unroll
+  for (int kl = 0; kl < 36; kl++) ctan[kl * ngp + q] = mat.C[kl];
+  ftrial[q] = fmax;
+  its[q] = 0;
+  its[ngp + q] = 0;
+  its[2 * ngp + q] = 0;
+  rn[q] = 0.;
+}
+
+// ordered compaction by one block: cnt[0] = flagged points; when used + cnt[0] <= cap they get the
+// slots used, used + 1, ... in ascending point order and cnt[1] = points to solve (list, ascending);
+// otherwise the flags are withdrawn and cnt[1] = -1 (the host reports the pool as too small)
+__global__ __launch_bounds__(1024) void k_mnl_compact(int64_t ngp, int* __restrict__ slot, int* __restrict__ list,
+                                                      int* __restrict__ cnt, int used, int cap) {
+  __shared__ int swn[16], swa[16], stot;
+  const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
+  const unsigned long long below = (1ull << lane) - 1ull;
+  int mine = 0;
+  for (int64_t q = tid; q < ngp; q += 1024) mine += slot[q] == -2;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) mine += __shfl_xor(mine, o, 64);
+  if (lane == 0) swn[w] = mine;
+  __syncthreads();
+  if (tid == 0) {
+    int t = 0;
+    for (int i = 0; i < 16; i++) t += swn[i];
+    stot = t;
+  }
+  __syncthreads();
+  const int total = stot;
+  const bool fits = (int64_t)used + total <= cap;
+  __syncthreads();
+  int base_n = used, base_a = 0;
+  for (int64_t b0 = 0; b0 < ngp; b0 += 1024) {
+    const int64_t q = b0 + tid;
+    const int sl = q < ngp ? slot[q] : -1;
+    const bool isn = sl == -2, isa = fits && (sl >= 0 || isn);
+    const unsigned long long bn = __ballot(isn), ba = __ballot(isa);
+    if (lane == 0) {
+      swn[w] = __popcll(bn);
+      swa[w] = __popcll(ba);
+    }
+    __syncthreads();
+    int pn = base_n + __popcll(bn & below), pa = base_a + __popcll(ba & below), tn = 0, ta = 0;
+    for (int i = 0; i < 16; i++) {
+      if (i < w) {
+        pn += swn[i];
+        pa += swa[i];
+      }
+      tn += swn[i];
+      ta += swa[i];
+    }
+    if (isn) slot[q] = fits ? pn : -1;
+    if (isa) list[pa] = (int)q;
+    base_n += tn;
+    base_a += ta;
+    __syncthreads();
+  }
+  if (tid == 0) {
+    cnt[0] = total;
+    cnt[1] = fits ? base_a : -1;
+    cnt[2] = 0;
+  }
+}
+
+__device__ __forceinline__ double mnl_reduce_max(double v, double* sred) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const double t = __shfl_xor(v, o, 64);
+    v = t > v ? t : v;
+  }
+  if ((threadIdx.x & 63) == 0) sred[threadIdx.x >> 6] = v;
+  __syncthreads();
+  double r = sred[0];
+  for (int q = 1; q < MICRO_TPB / 64; q++) r = sred[q] > r ? sred[q] : r;
+  __syncthreads();
+  return r;
+}
+
+// v = E x on the boundary nodes, 0 inside
+__device__ __forceinline__ void mnl_boundary(double* __restrict__ v, int n, const double (&Eb)[3][3]) {
+  const int ne = n - 1, nn = n * n * n;
+  for (int nd = threadIdx.x; nd < nn; nd += MICRO_TPB) {
+    const int i = nd % n, j = (nd / n) % n, k = nd / (n * n);
+    const bool bnd = i == 0 || j == 0 || k == 0 || i == ne || j == ne || k == ne;
+    const double X[3] = {(double)i / (double)ne, (double)j / (double)ne, (double)k / (double)ne};
+#pragma unroll
+    for (int r = 0; r < 3; r++) v[3 * nd + r] = bnd ? Eb[r][0] * X[0] + Eb[r][1] * X[1] + Eb[r][2] * X[2] : 0.;
+  }
+}
+
+// work stresses of the slot = C_gp B v at every micro Gauss point (the frozen tangents of the slot)
+__device__ __forceinline__ void mnl_apply_tangent(double* __restrict__ ws, const double* __restrict__ sdn,
+                                                  const unsigned char* __restrict__ sph, const double* __restrict__ v,
+                                                  int n, const double (&Gp)[2], const double (&Kp)[2]) {
+  const int ne = n - 1, nmgp = 8 * ne * ne * ne;
+  for (int mg = threadIdx.x; mg < nmgp; mg += MICRO_TPB) {
+    const int e = mg >> 3, gp = mg & 7, ph = sph[e];
+    double ee[6], nv[6], s[6];
+    mnl_strain(sdn + 24 * gp, v, n, e % ne, (e / ne) % ne, e / (ne * ne), ee);
+    const double th = ws[(size_t)MNL_TAN * nmgp + mg], thb = ws[(size_t)(MNL_TAN + 1) * nmgp + mg];
+#pragma unroll
+    for (int b = 0; b < 6; b++) nv[b] = ws[(size_t)(MNL_TAN + 2 + b) * nmgp + mg];
+    mnl_Cmul(ph ? Gp[1] : Gp[0], ph ? Kp[1] : Kp[0], th, thb, nv, ee, s);
+#pragma unroll
+    for (int k = 0; k < 6; k++) ws[(size_t)(MNL_SIG + k) * nmgp + mg] = s[k];
+  }
+}
+
+// y = sum over the node's elements (ascending) and their Gauss points of B_a^T sigma detJ, from
+// the slot's work stresses
+__device__ __forceinline__ void mnl_gather(const double* __restrict__ ws, const double* __restrict__ sdn, int n, int i,
+                                           int j, int k, double detJ, double (&y)[3]) {
+  const int ne = n - 1, nmgp = 8 * ne * ne * ne;
+  const double* sg = ws + (size_t)MNL_SIG * nmgp;
+  y[0] = y[1] = y[2] = 0.;
+#pragma unroll 1
+  for (int oz = 1; oz >= 0; oz--) {
+    const int ek = k - oz;
+    if (ek < 0 || ek >= ne) continue;
+#pragma unroll 1
+    for (int oy = 1; oy >= 0; oy--) {
+      const int ej = j - oy;
+      if (ej < 0 || ej >= ne) continue;
+#pragma unroll 1
+      for (int ox = 1; ox >= 0; ox--) {
+        const int ei = i - ox;
+        if (ei < 0 || ei >= ne) continue;
+        const int a = ox + 2 * oy + 4 * oz, mg0 = 8 * (ei + ne * (ej + ne * ek));
+#pragma unroll 1
+        for (int gp = 0; gp < 8; gp++) {
+          const double* dn = sdn + 24 * gp + 3 * a;
+          const double* s = sg + mg0 + gp;
+          const double s0 = s[0], s1 = s[nmgp], s2 = s[2 * (size_t)nmgp], s3 = s[3 * (size_t)nmgp],
+                       s4 = s[4 * (size_t)nmgp], s5 = s[5 * (size_t)nmgp];
+          y[0] += (dn[0] * s0 + dn[1] * s3 + dn[2] * s4) * detJ;
+          y[1] += (dn[1] * s1 + dn[0] * s3 + dn[2] * s5) * detJ;
+          y[2] += (dn[2] * s2 + dn[0] * s4 + dn[1] * s5) * detJ;
+        }
+      }
+    }
+  }
+}
+
+// the diagonal of K_T at node (i, j, k) from the slot's tangent data
+__device__ __forceinline__ void mnl_diag(const double* __restrict__ ws, const double* __restrict__ sdn,
+                                         const unsigned char* __restrict__ sph, int n, int i, int j, int k, double detJ,
+                                         const double (&Gp)[2], const double (&Kp)[2], double (&dg)[3]) {
+  const int ne = n - 1, nmgp = 8 * ne * ne * ne;
+  dg[0] = dg[1] = dg[2] = 0.;
+#pragma unroll 1
+  for (int oz = 1; oz >= 0; oz--)
+#pragma unroll 1
+    for (int oy = 1; oy >= 0; oy--)
+#pragma unroll 1
+      for (int ox = 1; ox >= 0; ox--) {
+        const int ei = i - ox, ej = j - oy, ek = k - oz;
+        if (ei < 0 || ej < 0 || ek < 0 || ei >= ne || ej >= ne || ek >= ne) continue;
+        const int a = ox + 2 * oy + 4 * oz, e = ei + ne * (ej + ne * ek), ph = sph[e];
+#pragma unroll 1
+        for (int gp = 0; gp < 8; gp++) {
+          const int mg = 8 * e + gp;
+          const double* dn = sdn + 24 * gp + 3 * a;
+          const double th = ws[(size_t)MNL_TAN * nmgp + mg], thb = ws[(size_t)(MNL_TAN + 1) * nmgp + mg];
+          double nv[6];
+#pragma unroll
+          for (int b = 0; b < 6; b++) nv[b] = ws[(size_t)(MNL_TAN + 2 + b) * nmgp + mg];
+          const double bc[3][6] = {{dn[0], 0., 0., dn[1], dn[2], 0.},
+                                   {0., dn[1], 0., dn[0], 0., dn[2]},
+                                   {0., 0., dn[2], 0., dn[0], dn[1]}};
+#pragma unroll
+          for (int r = 0; r < 3; r++) {
+            double s[6], t = 0.;
+            mnl_Cmul(ph ? Gp[1] : Gp[0], ph ? Kp[1] : Kp[0], th, thb, nv, bc[r], s);
+#pragma unroll
+            for (int b = 0; b < 6; b++) t += bc[r][b] * s[b];
+            dg[r] += t * detJ;
+          }
+        }
+      }
+}
+
+__global__ __launch_bounds__(MICRO_TPB) void k_mnl_solve(MicroNlArgs a, int64_t ngp, const int* __restrict__ list,
+                                                         const int* __restrict__ slot, const double* __restrict__ eps,
+                                                         double* __restrict__ sig, double* __restrict__ ctan,
+                                                         double* __restrict__ ftrial, double* __restrict__ pool,
+                                                         int* __restrict__ its_out, double* __restrict__ rn_out,
+                                                         int* __restrict__ cnt) {
+  __shared__ double su[MICRO_DOFS], sx[MICRO_DOFS], sr[MICRO_DOFS], sp[MICRO_DOFS], sq[MICRO_DOFS], sd[MICRO_DOFS];
+  __shared__ double sdn[8 * 24];
+  __shared__ double sred[2 * (MICRO_TPB / 64)];
+  __shared__ double scol[36];
+  __shared__ unsigned char sph[(MICRO_NMAX - 1) * (MICRO_NMAX - 1) * (MICRO_NMAX - 1)];
+  const int tid = threadIdx.x;
+  const int n = a.m.n, ne = n - 1, nn = n * n * n, ndof = 3 * nn, nel = ne * ne * ne, nmgp = 8 * nel;
+  if (n < 2 || n > MICRO_NMAX) return;  // (the host refuses these sizes before the launch)
+  const int64_t q = list[blockIdx.x];
+  double* ws = pool + (size_t)slot[q] * MNL_WS * nmgp;
+  const double detJ = 1. / (8. * (double)nel);
+  const double Gp[2] = {a.m.E[0] / (2. * (1. + a.m.nu[0])), a.m.E[1] / (2. * (1. + a.m.nu[1]))};
+  const double Kp[2] = {a.m.E[0] / (3. * (1. - 2. * a.m.nu[0])), a.m.E[1] / (3. * (1. - 2. * a.m.nu[1]))};
+
+  for (int e = tid; e < nel; e += MICRO_TPB)
+    sph[e] = (unsigned char)micro_phase(a.m.type, ne, e % ne, (e / ne) % ne, e / (ne * ne));
+  for (int t = tid; t < 8 * 24; t += MICRO_TPB) sdn[t] = mnl_dn(t, ne);
+  {
+    double em[6];
+#pragma unroll
+    for (int l = 0; l < 6; l++) em[l] = eps[l * ngp + q];
+    const double Eb[3][3] = {{em[0], em[3] / 2., em[4] / 2.}, {em[3] / 2., em[1], em[5] / 2.}, {em[4] / 2., em[5] / 2., em[2]}};
+    mnl_boundary(su, n, Eb);
+  }
+  for (int d = tid; d < ndof; d += MICRO_TPB) sd[d] = 0.;
+  __syncthreads();
+
+  // one loop, one CG: Newton steps (lc < 0), then the six frozen-tangent load cases lc = 0..5
+  int lc = -1, nits = 0, cgits = 0, status = 0;
+  double nnorm0 = 0., nrel = 0., fmax = -1e300;
+  for (;;) {
+    if (lc < 0) {
+      // state at the iterate su: stresses, new histories and tangent data of every micro point
+      fmax = -1e300;
+      for (int mg = tid; mg < nmgp; mg += MICRO_TPB) {
+        const int e = mg >> 3, gp = mg & 7, ph = sph[e];
+        double ee[6], h[7], s[6], hn[7], nv[6], th, thb;
+        mnl_strain(sdn + 24 * gp, su, n, e % ne, (e / ne) % ne, e / (ne * ne), ee);
+#pragma unroll
+        for (int i = 0; i < 7; i++) h[i] = ws[(size_t)(MNL_H0 + i) * nmgp + mg];
+        const double f = j2_point(ph ? Gp[1] : Gp[0], ph ? Kp[1] : Kp[0], ph ? a.Sy[1] : a.Sy[0],
+                                  ph ? a.Ka[1] : a.Ka[0], ee, h, s, hn, th, thb, nv);
+        fmax = f > fmax ? f : fmax;
+#pragma unroll
+        for (int i = 0; i < 7; i++) ws[(size_t)(MNL_H1 + i) * nmgp + mg] = hn[i];
+        ws[(size_t)MNL_TAN * nmgp + mg] = th;
+        ws[(size_t)(MNL_TAN + 1) * nmgp + mg] = thb;
+#pragma unroll
+        for (int b = 0; b < 6; b++) ws[(size_t)(MNL_TAN + 2 + b) * nmgp + mg] = nv[b];
+#pragma unroll
+        for (int k = 0; k < 6; k++) ws[(size_t)(MNL_SIG + k) * nmgp + mg] = s[k];
+      }
+      for (int d = tid; d < ndof; d += MICRO_TPB) sx[d] = 0.;
+      __syncthreads();
+      if (nits == 0) {  // D: the diagonal of K_T at the first iterate, kept for every later solve
+        for (int nd = tid; nd < nn; nd += MICRO_TPB) {
+          const int i = nd % n, j = (nd / n) % n, k = nd / (n * n);
+          if (i == 0 || j == 0 || k == 0 || i == ne || j == ne || k == ne) continue;
+          double dg[3];
+          mnl_diag(ws, sdn, sph, n, i, j, k, detJ, Gp, Kp, dg);
+#pragma unroll
+          for (int r = 0; r < 3; r++) sd[3 * nd + r] = 1. / dg[r];
+        }
+        __syncthreads();
+      }
+    } else {
+      double Eb[3][3];
+      const int p = lc == 5 ? 1 : 0, p2 = lc == 3 ? 1 : 2;  // xy: (0, 1), xz: (0, 2), yz: (1, 2)
+#pragma unroll
+      for (int r = 0; r < 3; r++)
+#pragma unroll
+        for (int d = 0; d < 3; d++)
+          Eb[r][d] = lc < 3 ? ((r == lc && d == lc) ? 1. : 0.) : (((r == p && d == p2) || (r == p2 && d == p)) ? 0.5 : 0.);
+      mnl_boundary(sx, n, Eb);
+      __syncthreads();
+      mnl_apply_tangent(ws, sdn, sph, sx, n, Gp, Kp);
+      __syncthreads();
+    }
+    // r = -(internal force) on the interior, p = z = D^-1 r
+    double rz = 0., zz = 0.;
+    for (int nd = tid; nd < nn; nd += MICRO_TPB) {
+      const int i = nd % n, j = (nd / n) % n, k = nd / (n * n);
+      const bool bnd = i == 0 || j == 0 || k == 0 || i == ne || j == ne || k == ne;
+      double y[3] = {0., 0., 0.};
+      if (!bnd) mnl_gather(ws, sdn, n, i, j, k, detJ, y);
+#pragma unroll
+      for (int r = 0; r < 3; r++) {
+        const double rr = bnd ? 0. : -y[r], z = sd[3 * nd + r] * rr;
+        sr[3 * nd + r] = rr;
+        sp[3 * nd + r] = z;
+        sq[3 * nd + r] = 0.;
+        rz += rr * z;
+        zz += z * z;
+      }
+    }
+    micro_reduce2(rz, zz, sred);
+    const double norm0 = sqrt(zz);
+    if (lc < 0) {
+      if (nits == 0) nnorm0 = norm0;
+      nrel = nnorm0 == 0. ? 0. : norm0 / nnorm0;
+      if (nnorm0 == 0. || nrel <= a.nl_rtol) {
+        // converged: the volume average of the micro stresses (the cell's volume is 1), then the tangent
+        double sg[6] = {0., 0., 0., 0., 0., 0.};
+        for (int mg = tid; mg < nmgp; mg += MICRO_TPB)
+#pragma unroll
+          for (int k = 0; k < 6; k++) sg[k] += ws[(size_t)(MNL_SIG + k) * nmgp + mg] * detJ;
+        micro_reduce2(sg[0], sg[1], sred);
+        micro_reduce2(sg[2], sg[3], sred);
+        micro_reduce2(sg[4], sg[5], sred);
+        fmax = mnl_reduce_max(fmax, sred);
+        if (tid == 0) {
+#pragma unroll
+          for (int k = 0; k < 6; k++) sig[k * ngp + q] = sg[k];
+          ftrial[q] = fmax;
+        }
+        lc = 0;
+        continue;
+      }
+      if (nits >= a.nl_max_it) {
+        status = 1;
+        break;
+      }
+    }
+    // Jacobi-CG on K_T,ii x = r from the guess in sx (zero inside)
+    int its = 0, conv = norm0 == 0.;
+    while (!conv && its < a.m.max_it) {
+      mnl_apply_tangent(ws, sdn, sph, sp, n, Gp, Kp);
+      __syncthreads();
+      double pq = 0., dummy = 0.;
+      for (int nd = tid; nd < nn; nd += MICRO_TPB) {
+        const int i = nd % n, j = (nd / n) % n, k = nd / (n * n);
+        if (i == 0 || j == 0 || k == 0 || i == ne || j == ne || k == ne) continue;  // q stays 0
+        double y[3];
+        mnl_gather(ws, sdn, n, i, j, k, detJ, y);
+#pragma unroll
+        for (int r = 0; r < 3; r++) {
+          sq[3 * nd + r] = y[r];
+          pq += sp[3 * nd + r] * y[r];
+        }
+      }
+      micro_reduce2(pq, dummy, sred);
+      if (!(pq > 0.)) break;  // no curvature left along p: reported as not converged
+      const double alpha = rz / pq;
+      double rz2 = 0., zz2 = 0.;
+      for (int d = tid; d < ndof; d += MICRO_TPB) {
+        sx[d] += alpha * sp[d];
+        const double rr = sr[d] - alpha * sq[d], z = sd[d] * rr;
+        sr[d] = rr;
+        rz2 += rr * z;
+        zz2 += z * z;
+      }
+      micro_reduce2(rz2, zz2, sred);
+      its++;
+      if (sqrt(zz2) / norm0 <= a.m.rtol) {
+        conv = 1;
+        break;
+      }
+      const double beta = rz2 / rz;
+      rz = rz2;
+      for (int d = tid; d < ndof; d += MICRO_TPB) sp[d] = sd[d] * sr[d] + beta * sp[d];
+      __syncthreads();
+    }
+    __syncthreads();
+    cgits += its;
+    if (!conv) {
+      status = 2;
+      break;
+    }
+    if (lc < 0) {
+      for (int d = tid; d < ndof; d += MICRO_TPB) su[d] += sx[d];
+      nits++;
+      __syncthreads();
+      continue;
+    }
+    // column lc of the tangent: the volume average of C_gp B w
+    mnl_apply_tangent(ws, sdn, sph, sx, n, Gp, Kp);
+    __syncthreads();
+    double sg[6] = {0., 0., 0., 0., 0., 0.};
+    for (int mg = tid; mg < nmgp; mg += MICRO_TPB)
+#pragma unroll
+      for (int k = 0; k < 6; k++) sg[k] += ws[(size_t)(MNL_SIG + k) * nmgp + mg] * detJ;
+    micro_reduce2(sg[0], sg[1], sred);
+    micro_reduce2(sg[2], sg[3], sred);
+    micro_reduce2(sg[4], sg[5], sred);
+    if (tid == 0)
+#pragma unroll
+      for (int k = 0; k < 6; k++) scol[k * 6 + lc] = sg[k];
+    __syncthreads();
+    if (++lc == 6) break;
+  }
+  if (status == 0 && tid < 36) ctan[tid * ngp + q] = 0.5 * (scol[tid] + scol[(tid % 6) * 6 + tid / 6]);
+  if (tid == 0) {
+    its_out[q] = nits;
+    its_out[ngp + q] = cgits;
+    its_out[2 * ngp + q] = status;
+    rn_out[q] = nrel;
+    if (status) atomicAdd(cnt + 2, 1);
+  }
+}
+
+// mcx_update_vars: the new histories become the committed ones in every used slot
+__global__ __launch_bounds__(TPB) void k_mnl_commit(double* __restrict__ pool, int64_t per_slot, int64_t nh,
+                                                    int64_t total) {
+  const int64_t t = (int64_t)blockIdx.x * TPB + threadIdx.x;
+  if (t >= total) return;
+  double* ws = pool + (t / nh) * per_slot;  // MNL_H0 = 0, MNL_H1 = 7: the first nh doubles take the next nh
+  ws[t % nh] = ws[nh + t % nh];
 }
 
 // One 3x3 block A(node g, node g+d) of the assembled matrix (MatSetValuesLocal(ADD) +
@@ -5846,7 +6397,34 @@ void launch_elastic_ke(Ctx& c) {
 }
 
 void launch_micro_rve(Ctx& c, const MicroArgs& m) {
-  hipLaunchKernelGGL(k_micro_rve, dim3(6), dim3(MICRO_TPB), 0, c.stream, m, c.micro_out);
+  hipLaunchKernelGGL(k_micro_rve, dim3(6), dim3(MICRO_TPB), 0, c.stream, m, c.micro_out, c.mnl_ufield);
+}
+
+void launch_mnl_conc(Ctx& c, const MicroNlArgs& a) {
+  const int ne = a.m.n - 1, nmgp = 8 * ne * ne * ne;
+  hipLaunchKernelGGL(k_mnl_conc, dim3((nmgp + 255) / 256), dim3(256), 0, c.stream, a, c.mnl_ufield, c.mnl_conc);
+}
+
+void launch_mnl_linear(Ctx& c, const MicroNlArgs& a) {
+  const int64_t ngp = 8 * c.g.nelem;
+  const int ne = a.m.n - 1, nmgp = 8 * ne * ne * ne;
+  hipLaunchKernelGGL(k_mnl_linear, dim3(nblk(ngp)), dim3(TPB), 0, c.stream, ngp, c.mat, nmgp, c.mnl_conc, c.eps,
+                     c.mnl_slot, c.sig, c.ctan, c.ftrial, c.mnl_its, c.mnl_rn);
+  hipLaunchKernelGGL(k_mnl_compact, dim3(1), dim3(1024), 0, c.stream, ngp, c.mnl_slot, c.mnl_list, c.mnl_cnt,
+                     (int)c.mnl_used, (int)c.mnl_cap);
+}
+
+void launch_mnl_solve(Ctx& c, const MicroNlArgs& a, int nsolve) {
+  hipLaunchKernelGGL(k_mnl_solve, dim3(nsolve), dim3(MICRO_TPB), 0, c.stream, a, (int64_t)(8 * c.g.nelem), c.mnl_list,
+                     c.mnl_slot, c.eps, c.sig, c.ctan, c.ftrial, c.mnl_pool, c.mnl_its, c.mnl_rn, c.mnl_cnt);
+}
+
+void launch_mnl_commit(Ctx& c, const MicroNlArgs& a) {
+  const int ne = a.m.n - 1;
+  const int64_t nmgp = 8 * ne * ne * ne, nh = 7 * nmgp, total = nh * c.mnl_used;
+  if (total > 0)
+    hipLaunchKernelGGL(k_mnl_commit, dim3(nblk(total)), dim3(TPB), 0, c.stream, c.mnl_pool, (int64_t)MNL_WS * nmgp, nh,
+                       total);
 }
 
 // element matrices of a per-GP-tangent law (k_element_ke), read by the gathers below

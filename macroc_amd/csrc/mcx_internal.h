@@ -76,6 +76,19 @@ __host__ __device__ inline int micro_phase(int type, int ne, int i, int j, int k
   return 2 * j + 1 < ne;
 }
 
+// -mat_law micro_nl: the same cell with J2-plastic phases, solved per macro Gauss point.
+// A solved point owns a slot of the pool: MNL_WS doubles per micro Gauss point, component-major
+// ([comp][8 (n-1)^3]): committed history 7, new history 7, tangent data 8 (theta, theta-bar, n[6]),
+// work stresses 6
+constexpr int MNL_H0 = 0, MNL_H1 = 7, MNL_TAN = 14, MNL_SIG = 22, MNL_WS = 28;
+constexpr int MNL_CONC = 38;  // per micro Gauss point: strain concentration 6x6, 2G, sqrt(2/3) Sy
+struct MicroNlArgs {
+  MicroArgs m;          // the cell, phase E / nu, the CG's rtol and max_it
+  double Sy[2], Ka[2];
+  double nl_rtol;       // Newton: |D^-1 R| <= nl_rtol |D^-1 R_0|
+  int nl_max_it;
+};
+
 struct HaloPlan {
   std::vector<int> nbr_rank;          // neighbour ranks (<= 26)
   std::vector<int64_t> send_off, send_cnt, recv_off, recv_cnt;  // in nodes
@@ -370,6 +383,24 @@ struct Ctx {
   int micro_its[6] = {};
   double micro_rnorm[6] = {};
 
+  // -mat_law micro_nl: phase Sy / Ka and the Newton settings; the unit-strain fields' strain
+  // concentration tensors (with C_hom, after ensure_micro); the slot of every local Gauss point
+  // (-1: linear shortcut), the compacted list of points to solve, the pool (allocated at the first
+  // non-linear point) and each point's solver record
+  double mnl_Sy[2] = {}, mnl_Ka[2] = {};
+  double mnl_rtol = 1e-10;
+  int mnl_max_it = 20;
+  int64_t mnl_slots_opt = 0;     // option micro_nl_slots (0: what fits 2 GiB, at most the local Gauss points)
+  int64_t mnl_cap = 0, mnl_used = 0;
+  double* mnl_ufield = nullptr;  // [6][3 n^3] unit-strain solutions
+  double* mnl_conc = nullptr;    // [MNL_CONC][8 (n-1)^3]
+  int* mnl_slot = nullptr;       // [ngp]
+  int* mnl_list = nullptr;       // [ngp] points to solve, ascending
+  int* mnl_cnt = nullptr;        // [2] new points, points to solve
+  int* mnl_its = nullptr;        // [3][ngp] Newton iterations, CG iterations, status (0 ok, 1 Newton, 2 CG)
+  double* mnl_rn = nullptr;      // [ngp] final relative Newton residual
+  double* mnl_pool = nullptr;    // [mnl_cap][MNL_WS][8 (n-1)^3]
+
   // external Gauss-point law (-mat_law external): host MicroPP-shaped callbacks or a device law
   mcx_micropp_api mpp{};
   bool has_mpp = false;
@@ -432,6 +463,11 @@ void launch_element_ke(Ctx& c);        // Ke of a per-GP-tangent law
 int launch_plain_ke(Ctx& c);           // plain elements, kref, the other elements' Ke (exception-node build)
 void launch_elastic_ke(Ctx& c);        // the elastic law's one element matrix (ke_uni); -mat_law micro: from C_hom
 void launch_micro_rve(Ctx& c, const MicroArgs& m);  // the six unit-strain solves of the micro cell -> micro_out
+// -mat_law micro_nl
+void launch_mnl_conc(Ctx& c, const MicroNlArgs& a);    // mnl_ufield -> mnl_conc
+void launch_mnl_linear(Ctx& c, const MicroNlArgs& a);  // linear test, sigma = C_hom eps, compaction -> mnl_cnt
+void launch_mnl_solve(Ctx& c, const MicroNlArgs& a, int nsolve);
+void launch_mnl_commit(Ctx& c, const MicroNlArgs& a);  // new history -> committed history, used slots
 void launch_gather_matrix(Ctx& c);
 void launch_gather_matrix_sym(Ctx& c);
 int build_split(Ctx& c, bool* exact);  // AIJ-split corrections from U (exact = usable)

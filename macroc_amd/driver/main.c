@@ -164,15 +164,24 @@ static int run(int argc, char** argv) {
     return 2;
   }
 #endif
-  if (o.mat_law == MCX_LAW_MICRO) { /* src/init.c:196-213 with the micro cell solved on the device */
+  if (o.mat_law == MCX_LAW_MICRO || o.mat_law == MCX_LAW_MICRO_NL) {
+    /* src/init.c:196-213 with the micro cell solved on the device */
+    const int nl = o.mat_law == MCX_LAW_MICRO_NL; /* J2-plastic phases, one cell solve per Gauss point */
     CHK(mcx_material_set(ctx, 0, o.micro_mat_1[0], o.micro_mat_1[1], o.micro_mat_1[2], o.micro_mat_1[3], 1));
     CHK(mcx_material_set(ctx, 1, o.micro_mat_2[0], o.micro_mat_2[1], o.micro_mat_2[2], o.micro_mat_2[3], 1));
     double chom[36], rn[6];
     int cg_its[6];
     CHK(mcx_micro_get_ctan(ctx, chom, cg_its, rn)); /* every rank solves its own, identical copy */
     PRINTF("Material Values : \n");
-    PRINTF("id 0 : E = %e\tnu = %e\n", o.micro_mat_1[0], o.micro_mat_1[1]);
-    PRINTF("id 1 : E = %e\tnu = %e\n", o.micro_mat_2[0], o.micro_mat_2[1]);
+    if (nl) {
+      PRINTF("id 0 : E = %e\tnu = %e\tSy = %e\tKa = %e\n", o.micro_mat_1[0], o.micro_mat_1[1], o.micro_mat_1[2],
+             o.micro_mat_1[3]);
+      PRINTF("id 1 : E = %e\tnu = %e\tSy = %e\tKa = %e\n", o.micro_mat_2[0], o.micro_mat_2[1], o.micro_mat_2[2],
+             o.micro_mat_2[3]);
+    } else {
+      PRINTF("id 0 : E = %e\tnu = %e\n", o.micro_mat_1[0], o.micro_mat_1[1]);
+      PRINTF("id 1 : E = %e\tnu = %e\n", o.micro_mat_2[0], o.micro_mat_2[1]);
+    }
     PRINTF("Micro cell : type = %d (%s)\tn = %d\n", o.micro_type, o.micro_type == 0 ? "sphere" : "layer", o.micro_n);
     PRINTF("C_hom : \n");
     for (int k = 0; k < 6; k++)
