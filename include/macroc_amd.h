@@ -286,7 +286,8 @@ int mcx_get_gp_strain(void* ctx, double* host /* [ngp][6] */);
 int mcx_get_gp_ctan(void* ctx, double* host /* [ngp][36] */);
 
 /* ---- the micro-scale cell (-mat_law micro) ----
- * The unit cube with micro_n nodes per edge (2 <= micro_n <= 10), ne = micro_n - 1 Q1 hexahedra per
+ * The unit cube with micro_n nodes per edge (2 <= micro_n <= 10; <= 20 with the option "micro_mem" 1,
+ * below), ne = micro_n - 1 Q1 hexahedra per
  * edge, 2x2x2 Gauss points, physical B.  Material 0 is micro_mat_1, material 1 micro_mat_2 (E, nu;
  * isotropic elastic, Sy and Ka unused).  Element (i, j, k), 0 <= i, j, k < ne, is of material 1 iff
  *   micro_type 0 (centred sphere, radius 0.5): (2i+1-ne)^2 + (2j+1-ne)^2 + (2k+1-ne)^2 < ne^2
@@ -299,7 +300,13 @@ int mcx_get_gp_ctan(void* ctx, double* host /* [ngp][36] */);
  * is the volume average of the Gauss-point stresses; C_hom = (C + C^T) / 2.  It is computed on
  * the device at the first mcx_homogenize, mcx_assembly_jac or mcx_micro_get_ctan after mcx_init
  * and again after mcx_material_set or a micro_* option changed it; every context of a multi-rank
- * run computes its own, bit-identical copy. */
+ * run computes its own, bit-identical copy.
+ * "micro_mem" (mcx_set_option; -micro_mem lds|device through mcx_apply_args): 0 (default) keeps the
+ * cell solvers' nodal vectors in LDS, which bounds micro_n by 10; 1 keeps them in a device-memory
+ * workspace (six of 5 x 3 micro_n^3 doubles here; for -mat_law micro_nl min(2 x compute units,
+ * local Gauss points) of 6 x 3 micro_n^3 doubles, whatever the number of solved points) and
+ * accepts micro_n <= 20.  For micro_n <= 10 both give the same bits.  The option recomputes C_hom
+ * and is refused while history slots of -mat_law micro_nl are in use. */
 /* C_hom (row major, C[k*6+l]) and, per load case, the CG iterations and the final relative
    preconditioned residual norm.  Any pointer may be NULL. */
 int mcx_micro_get_ctan(void* ctx, double C[36], int its[6], double rnorm[6]);
@@ -392,10 +399,15 @@ int mcx_set_timing(void* ctx, int on);
 int mcx_get_timing(void* ctx, mcx_timing* t);
 int mcx_synchronize(void* ctx);
 /* tuning knobs ("spmv_subl": lines per sub-slab of the SpMV sweep, 0 = whole XCD slab; "micro_rtol",
-   "micro_max_it": the micro cell's CG, -mat_law micro; "micro_nl_rtol", "micro_nl_max_it", "micro_nl_slots":
+   "micro_max_it", "micro_mem": the micro cell's CG, -mat_law micro; "micro_nl_rtol", "micro_nl_max_it", "micro_nl_slots":
    -mat_law micro_nl) and a
    device-only SpMV timer (iters launches on the current search direction, HIP events) */
 int mcx_set_option(void* ctx, const char* name, double value);
+/* the command-line flags that have no mcx_opts field, applied to a context through mcx_set_option:
+   -micro_mem lds|device ("micro_mem" 0 | 1), -micro_rtol, -micro_max_it, -micro_nl_rtol,
+   -micro_nl_max_it, -micro_nl_slots (each with a number).  mcx_parse_args accepts these flags and
+   checks -micro_mem's word; call this after mcx_init with the same argv.  Other flags are skipped. */
+int mcx_apply_args(void* ctx, int argc, const char* const* argv);
 int mcx_time_spmv(void* ctx, int iters, double* avg_ms);
 
 #ifdef __cplusplus

@@ -41,7 +41,7 @@ EXPORTS = [
     "mcx_set_timing", "mcx_get_timing", "mcx_synchronize", "mcx_set_option", "mcx_time_spmv",
     "mcx_set_micropp", "mcx_set_device_law", "mcx_set_gp_stress", "mcx_set_gp_ctan", "mcx_get_gp_strain",
     "mcx_micro_get_ctan", "mcx_micro_get_phase",
-    "mcx_get_gp_ctan", "mcx_micro_nl_get_info", "mcx_micro_nl_get_pool",
+    "mcx_get_gp_ctan", "mcx_micro_nl_get_info", "mcx_micro_nl_get_pool", "mcx_apply_args",
 ]
 
 LAWS = {"elastic": 0, "plastic": 1, "external": 2, "micro": 3, "micro_nl": 4}
@@ -180,6 +180,7 @@ def lib():
     L.mcx_set_timing.argtypes = [vp, C.c_int]
     L.mcx_get_timing.argtypes = [vp, C.POINTER(Timing)]
     L.mcx_set_option.argtypes = [vp, C.c_char_p, C.c_double]
+    L.mcx_apply_args.argtypes = [vp, C.c_int, C.POINTER(C.c_char_p)]
     L.mcx_time_spmv.argtypes = [vp, C.c_int, d]
     L.mcx_set_micropp.argtypes = [vp, C.POINTER(MicroppApi)]
     L.mcx_set_device_law.argtypes = [vp, C.POINTER(DeviceLaw)]
@@ -285,6 +286,14 @@ class Macroc:
             _check(L.mcx_init_local(C.byref(self.opts), rank, group._g, C.byref(self._ctx)), "mcx_init_local")
         else:
             _check(L.mcx_init(C.byref(self.opts), rank, nranks, cid, C.byref(self._ctx)), "mcx_init")
+        if opts is None:  # the flags without an Opts field (-micro_mem, -micro_nl_slots, ...)
+            args = [str(a).encode() for a in argv]
+            arr = (C.c_char_p * max(len(args), 1))(*args)
+            rc = L.mcx_apply_args(self._ctx, len(args), arr)
+            if rc:
+                err = L.mcx_last_error().decode()
+                self.finish()
+                raise MacrocError(f"mcx_apply_args failed ({rc}): {err}")
         inf = Info()
         _check(L.mcx_get_info(self._ctx, C.byref(inf)), "mcx_get_info")
         self.info = inf.as_dict()

@@ -99,7 +99,7 @@ static int free_ctx(Ctx* c) {
   if (c->comm_stream) (void)hipStreamSynchronize(c->comm_stream);
   if (c->x_stream) (void)hipStreamSynchronize(c->x_stream);
   if (c->f_stream) (void)hipStreamSynchronize(c->f_stream);
-  void* ptrs[] = {c->micro_out, c->mnl_ufield, c->mnl_conc, c->mnl_slot, c->mnl_list, c->mnl_cnt, c->mnl_its, c->mnl_rn, c->mnl_pool, c->hist_old, c->hist_new, c->ftrial, c->b, c->du, c->r, c->z, c->w, c->jix, c->jdd, c->V, c->U, c->D, c->d_mask, c->vi_idx, c->wd, c->vi_dict, c->vi_keys, c->vi_slot, c->vi_ctl, c->vi_bdict, c->eps, c->sig, c->ctan, c->Ke,
+  void* ptrs[] = {c->micro_out, c->micro_ws, c->mnl_ws, c->mnl_ufield, c->mnl_conc, c->mnl_slot, c->mnl_list, c->mnl_cnt, c->mnl_its, c->mnl_rn, c->mnl_pool, c->hist_old, c->hist_new, c->ftrial, c->b, c->du, c->r, c->z, c->w, c->jix, c->jdd, c->V, c->U, c->D, c->d_mask, c->vi_idx, c->wd, c->vi_dict, c->vi_keys, c->vi_slot, c->vi_ctl, c->vi_bdict, c->eps, c->sig, c->ctan, c->Ke,
                   c->vib_keys, c->vib_ctl, c->vib_pos, c->ke_uni, c->xdone, c->esc_node, c->esc_res, c->esc_slot, c->elem_plain, c->cref, c->vi_xslot,
                   c->vi_xlist, c->vi_xcnt, c->vi_exc, c->st_coef, c->st_ids, c->st_slot, c->st_list, c->st_cnt, c->st_mask,
                   c->partials, c->red, c->red_loc, c->cg, c->hist, c->tmp, c->halo.d_send_idx,
@@ -250,9 +250,9 @@ static int init_ctx(Ctx& c, const mcx_opts* o, int rank, int nranks, const void*
     c.micro_dirty = true;
   }
   if (o->mat_law == MCX_LAW_MICRO_NL) {  // the pool itself waits for the first non-linear point
-    const int64_t ngp = 8 * E, mgp = 8 * (MICRO_NMAX - 1) * (MICRO_NMAX - 1) * (MICRO_NMAX - 1);
-    if ((rc = dalloc(c, &c.ftrial, ngp)) || (rc = dalloc(c, &c.mnl_ufield, 6 * MICRO_DOFS)) ||
-        (rc = dalloc(c, &c.mnl_conc, MNL_CONC * mgp)) || (rc = dalloc(c, &c.mnl_slot, ngp)) ||
+    // (the unit-strain fields and the concentration tensors follow the cell's size: ensure_micro)
+    const int64_t ngp = 8 * E;
+    if ((rc = dalloc(c, &c.ftrial, ngp)) || (rc = dalloc(c, &c.mnl_slot, ngp)) ||
         (rc = dalloc(c, &c.mnl_list, ngp)) || (rc = dalloc(c, &c.mnl_cnt, 4)) ||
         (rc = dalloc(c, &c.mnl_its, 3 * ngp)) || (rc = dalloc(c, &c.mnl_rn, ngp)))
       return rc;
@@ -383,6 +383,16 @@ static int cg_solve(Ctx& c, int* its, double* rnorm, int* reason) {
 
 using namespace mcx;
 
+// command-line flags that are options of a context (mcx_set_option names behind a '-'), not
+// mcx_opts fields: mcx_parse_args accepts them, mcx_apply_args applies them after mcx_init
+static const char* const kApplyFlags[] = {"-micro_mem",     "-micro_rtol",      "-micro_max_it",
+                                          "-micro_nl_rtol", "-micro_nl_max_it", "-micro_nl_slots"};
+static bool apply_flag(const char* k) {
+  for (const char* f : kApplyFlags)
+    if (!std::strcmp(k, f)) return true;
+  return false;
+}
+
 #define CTX(p) Ctx& c = *reinterpret_cast<Ctx*>(p)
 #define GUARD(p)                      \
   if (!(p)) {                         \
@@ -499,6 +509,14 @@ int mcx_parse_args(mcx_opts* o, int argc, const char* const* argv) try {
     }
     if (!std::strcmp(k, "-ksp_monitor")) {
       o->ksp_monitor = 1;
+      continue;
+    }
+    if (apply_flag(k)) {  // options of the context: mcx_apply_args sets them after mcx_init
+      if (!std::strcmp(k, "-micro_mem") && (!v || (std::strcmp(v, "lds") && std::strcmp(v, "device")))) {
+        set_error(std::string("-micro_mem: lds or device, got ") + (v ? v : "(none)"));
+        return 2;
+      }
+      a++;
       continue;
     }
     if (!std::strcmp(k, "-ksp_type") || !std::strcmp(k, "-pc_type")) {
@@ -799,14 +817,44 @@ static MicroNlArgs mnl_args(const Ctx& c) {
   return a;
 }
 
+// the largest micro_n of the memory mode in use (option micro_mem)
+static int micro_nmax(const Ctx& c) { return c.micro_mem ? MICRO_NMAX_DEV : MICRO_NMAX; }
+
+static int micro_n_refused(const Ctx& c) {
+  const int n = c.micro.n;
+  if (n >= 2 && n <= micro_nmax(c)) return 0;
+  std::string e = "-mat_law micro: -micro_n " + std::to_string(n) + " outside the supported range 2 <= micro_n <= " +
+                  std::to_string(micro_nmax(c));
+  if (c.micro_mem)
+    e += " (option micro_mem 1: one workgroup per cell with its CG state in device memory)";
+  else
+    e += " (option micro_mem 0: the cell's CG state has to fit one CU's LDS; micro_mem 1 / -micro_mem device keeps "
+         "it in device memory, up to micro_n " + std::to_string(MICRO_NMAX_DEV) + ")";
+  set_error(e);
+  return 31;
+}
+
+// (re)allocates a device array whose size follows the cell; bytes = what it holds now
+static int micro_resize(Ctx& c, double** p, int64_t* bytes, int64_t want) {
+  if (*p && *bytes == want) return 0;
+  if (*p) {
+    MCX_HIP(hipStreamSynchronize(c.stream));
+    MCX_HIP(hipFree(*p));
+    *p = nullptr;
+    c.device_bytes -= *bytes;
+    *bytes = 0;
+  }
+  if (want <= 0) return 0;
+  MCX_HIP(hipMalloc((void**)p, (size_t)want));
+  *bytes = want;
+  c.device_bytes += want;
+  return 0;
+}
+
 static int ensure_micro(Ctx& c) {
   if (!micro_law(c.mat.law) || !c.micro_dirty) return 0;
   MicroArgs m = c.micro;
-  if (m.n < 2 || m.n > MICRO_NMAX) {
-    set_error("-mat_law micro: -micro_n " + std::to_string(m.n) + " outside the supported range 2 <= micro_n <= " +
-              std::to_string(MICRO_NMAX) + " (the cell's CG state has to fit one CU's LDS)");
-    return 31;
-  }
+  if (int rc = micro_n_refused(c)) return rc;
   if (m.type != 0 && m.type != 1) {
     set_error("-mat_law micro: -micro_type " + std::to_string(m.type) +
               " is not implemented (0: centred sphere, 1: flat layer in y)");
@@ -814,6 +862,15 @@ static int ensure_micro(Ctx& c) {
   }
   const int interior = 3 * (m.n - 2) * (m.n - 2) * (m.n - 2);
   m.max_it = c.micro_max_it > 0 ? c.micro_max_it : 10 * interior;
+  const int64_t ndof = 3 * (int64_t)m.n * m.n * m.n, nmgp = 8 * (int64_t)(m.n - 1) * (m.n - 1) * (m.n - 1);
+  if (c.mat.law == MCX_LAW_MICRO_NL) {  // the unit-strain fields and their concentration tensors, for this n
+    int rc;
+    if ((rc = micro_resize(c, &c.mnl_ufield, &c.mnl_ufield_bytes, (int64_t)sizeof(double) * 6 * ndof)) ||
+        (rc = micro_resize(c, &c.mnl_conc, &c.mnl_conc_bytes, (int64_t)sizeof(double) * MNL_CONC * nmgp)))
+      return rc;
+  }
+  const int64_t rve_ws = c.micro_mem ? (int64_t)sizeof(double) * 6 * 5 * ndof : 0;  // micro_mem 1: six workspaces
+  if (int rc = micro_resize(c, &c.micro_ws, &c.micro_ws_bytes, rve_ws)) return rc;
   launch_micro_rve(c, m);
   MCX_HIP(hipGetLastError());
   double h[6 * MICRO_OUT];
@@ -894,6 +951,13 @@ static int micro_nl_homogenize(Ctx& c) {
     MCX_HIP(hipMalloc((void**)&c.mnl_pool, (size_t)(c.mnl_cap * bytes)));
     MCX_HIP(hipMemsetAsync(c.mnl_pool, 0, (size_t)(c.mnl_cap * bytes), c.stream));
     c.device_bytes += c.mnl_cap * bytes;
+  }
+  {  // micro_mem 1: one workspace of 6 nodal vectors per resident block (two blocks per compute unit)
+    c.mnl_ws_blocks = (int)std::min<int64_t>(c.mnl_ws_blocks_opt > 0 ? c.mnl_ws_blocks_opt : 2 * (int64_t)c.ncu, ngp);
+    const int64_t nn = (int64_t)a.m.n * a.m.n * a.m.n;
+    if (int rc = micro_resize(c, &c.mnl_ws, &c.mnl_ws_bytes,
+                              c.micro_mem ? (int64_t)sizeof(double) * c.mnl_ws_blocks * 6 * 3 * nn : 0))
+      return rc;
   }
   c.mnl_used += h[0];
   launch_mnl_solve(c, a, h[1]);
@@ -1113,7 +1177,7 @@ int mcx_micro_nl_get_pool(void* ctx, int64_t* slots_used, int64_t* slots_allocat
   if (int rc = need_micro_nl(c, "mcx_micro_nl_get_pool")) return rc;
   if (slots_used) *slots_used = c.mnl_used;
   if (slots_allocated) *slots_allocated = c.mnl_pool ? c.mnl_cap : 0;
-  if (bytes_per_slot) *bytes_per_slot = c.micro.n >= 2 && c.micro.n <= MICRO_NMAX ? mnl_slot_bytes(c) : 0;
+  if (bytes_per_slot) *bytes_per_slot = c.micro.n >= 2 && c.micro.n <= micro_nmax(c) ? mnl_slot_bytes(c) : 0;
   return 0;
 } MCX_CATCH
 
@@ -1143,11 +1207,7 @@ int mcx_micro_get_phase(void* ctx, unsigned char* phase, int64_t* n) try {
     return 7;
   }
   const int mn = c.micro.n, ne = mn - 1, type = c.micro.type;
-  if (mn < 2 || mn > MICRO_NMAX) {
-    set_error("-mat_law micro: -micro_n " + std::to_string(mn) + " outside the supported range 2 <= micro_n <= " +
-              std::to_string(MICRO_NMAX));
-    return 31;
-  }
+  if (int rc = micro_n_refused(c)) return rc;
   if (type != 0 && type != 1) {
     set_error("-mat_law micro: -micro_type " + std::to_string(type) +
               " is not implemented (0: centred sphere, 1: flat layer in y)");
@@ -1869,6 +1929,30 @@ int mcx_set_option(void* ctx, const char* name, double value) try {
     c.micro_dirty = true;
     return 0;
   }
+  if (!std::strcmp(name, "micro_mem_blocks")) {  // testing: micro_mem 1's workspaces (0: 2 x compute units)
+    if (!(value >= 0.) || value > 65535.) {
+      set_error("micro_mem_blocks: 0 .. 65535");
+      return 1;
+    }
+    c.mnl_ws_blocks_opt = (int)value;
+    return 0;
+  }
+  if (!std::strcmp(name, "micro_mem")) {  // where the cell solvers' nodal vectors live: 0 LDS, 1 device memory
+    if (value != 0. && value != 1.) {
+      set_error("micro_mem: 0 (the cell solvers' vectors in LDS, micro_n <= " + std::to_string(MICRO_NMAX) +
+                ") or 1 (in device memory, micro_n <= " + std::to_string(MICRO_NMAX_DEV) + ")");
+      return 1;
+    }
+    if ((int)value == c.micro_mem) return 0;
+    if (c.mnl_used > 0) {  // the histories would outlive the solver that wrote them
+      set_error("micro_mem: " + std::to_string(c.mnl_used) +
+                " history slots are in use; the memory mode is chosen before the first non-linear point");
+      return 2;
+    }
+    c.micro_mem = (int)value;
+    c.micro_dirty = true;  // C_hom and the concentration tensors are recomputed, the workspaces resized
+    return 0;
+  }
   if (!std::strcmp(name, "spmv_subl")) {
     const int old = c.spmv_subl;
     c.spmv_subl = (int)value;
@@ -2243,6 +2327,32 @@ int mcx_set_option(void* ctx, const char* name, double value) try {
   }
   set_error(std::string("unknown option ") + name);
   return 2;
+} MCX_CATCH
+
+// the command-line flags without an mcx_opts field (kApplyFlags): each goes through mcx_set_option
+int mcx_apply_args(void* ctx, int argc, const char* const* argv) try {
+  MCX_ENTRY();
+  if (!ctx) {
+    set_error("mcx_apply_args: null context");
+    return 1;
+  }
+  for (int a = 0; a + 1 < argc; a++) {
+    const char* k = argv[a];
+    if (!k || !argv[a + 1] || !apply_flag(k)) continue;
+    const char* v = argv[++a];
+    double value;
+    if (!std::strcmp(k, "-micro_mem")) {
+      if (std::strcmp(v, "lds") && std::strcmp(v, "device")) {
+        set_error(std::string("-micro_mem: lds or device, got ") + v);
+        return 2;
+      }
+      value = std::strcmp(v, "device") ? 0. : 1.;
+    } else {
+      value = std::atof(v);
+    }
+    if (int rc = mcx_set_option(ctx, k + 1, value)) return rc;
+  }
+  return 0;
 } MCX_CATCH
 
 int mcx_time_spmv(void* ctx, int iters, double* avg_ms) try {

@@ -708,16 +708,31 @@ __device__ __forceinline__ void micro_apply(const double* __restrict__ ske, cons
   }
 }
 
+//
+// DEV (option micro_mem 1): the five vectors are block lc's part of the workspace wsp
+// in device memory ([6][5][3 n^3] doubles) instead of LDS arrays, which lifts n from MICRO_NMAX to
+// MICRO_NMAX_DEV; the loops, the gather order and the reductions are the same statements, so both
+// instantiations give the same bits.  Every barrier that ordered the LDS traffic orders the
+// block's global traffic (__syncthreads fences the workgroup's global accesses too); wsp is not
+// __restrict__, its parts are one allocation.
+template <bool DEV>
 __global__ __launch_bounds__(MICRO_TPB) void k_micro_rve(MicroArgs m, double* __restrict__ out,
-                                                          double* __restrict__ ufield) {
-  __shared__ double sx[MICRO_DOFS], sr[MICRO_DOFS], sp[MICRO_DOFS], sq[MICRO_DOFS], sd[MICRO_DOFS];
+                                                          double* __restrict__ ufield, double* wsp) {
+  constexpr int NMAX = DEV ? MICRO_NMAX_DEV : MICRO_NMAX, LV = DEV ? 1 : MICRO_DOFS;
+  __shared__ double lx[LV], lr[LV], lp[LV], lq[LV], ld[LV];
   __shared__ double ske[2 * 576];
   __shared__ double sdn[8 * 24];  // [gp][a][d] physical shape-function gradients
   __shared__ double sred[2 * (MICRO_TPB / 64)];
-  __shared__ unsigned char sph[(MICRO_NMAX - 1) * (MICRO_NMAX - 1) * (MICRO_NMAX - 1)];
+  __shared__ unsigned char sph[(NMAX - 1) * (NMAX - 1) * (NMAX - 1)];
   const int tid = threadIdx.x, lc = blockIdx.x;
   const int n = m.n, ne = n - 1, nn = n * n * n, ndof = 3 * nn, nel = ne * ne * ne;
-  if (n < 2 || n > MICRO_NMAX || lc >= 6) return;  // (the host refuses these sizes before the launch)
+  if (n < 2 || n > NMAX || lc >= 6) return;  // (the host refuses these sizes before the launch)
+  double* const wb = DEV ? wsp + (size_t)lc * 5 * ndof : nullptr;
+  double* const sx = DEV ? wb : lx;
+  double* const sr = DEV ? wb + ndof : lr;
+  double* const sp = DEV ? wb + 2 * (size_t)ndof : lp;
+  double* const sq = DEV ? wb + 3 * (size_t)ndof : lq;
+  double* const sd = DEV ? wb + 4 * (size_t)ndof : ld;
   const double detJ = 1. / (8. * (double)nel);  // (h / 2)^3, h = 1 / ne
 
   for (int e = tid; e < nel; e += MICRO_TPB)
@@ -1199,22 +1214,34 @@ __device__ __forceinline__ void mnl_diag(const double* __restrict__ ws, const do
       }
 }
 
+//
+// DEV (option micro_mem 1): the six vectors are this block's workspace in device
+// memory (wsp, [gridDim.x][6][3 n^3] doubles) and the block walks the points blockIdx.x,
+// blockIdx.x + gridDim.x, ... of the list, so the workspace does not grow with the number of
+// points.  The block index selects memory only; no arithmetic sees it, the slot or the walk order.
+template <bool DEV>
 __global__ __launch_bounds__(MICRO_TPB) void k_mnl_solve(MicroNlArgs a, int64_t ngp, const int* __restrict__ list,
                                                          const int* __restrict__ slot, const double* __restrict__ eps,
                                                          double* __restrict__ sig, double* __restrict__ ctan,
                                                          double* __restrict__ ftrial, double* __restrict__ pool,
                                                          int* __restrict__ its_out, double* __restrict__ rn_out,
-                                                         int* __restrict__ cnt) {
-  __shared__ double su[MICRO_DOFS], sx[MICRO_DOFS], sr[MICRO_DOFS], sp[MICRO_DOFS], sq[MICRO_DOFS], sd[MICRO_DOFS];
+                                                         int* __restrict__ cnt, int nsolve, double* wsp) {
+  constexpr int NMAX = DEV ? MICRO_NMAX_DEV : MICRO_NMAX, LV = DEV ? 1 : MICRO_DOFS;
+  __shared__ double lu[LV], lx[LV], lr[LV], lp[LV], lq[LV], ld[LV];
   __shared__ double sdn[8 * 24];
   __shared__ double sred[2 * (MICRO_TPB / 64)];
   __shared__ double scol[36];
-  __shared__ unsigned char sph[(MICRO_NMAX - 1) * (MICRO_NMAX - 1) * (MICRO_NMAX - 1)];
+  __shared__ unsigned char sph[(NMAX - 1) * (NMAX - 1) * (NMAX - 1)];
   const int tid = threadIdx.x;
   const int n = a.m.n, ne = n - 1, nn = n * n * n, ndof = 3 * nn, nel = ne * ne * ne, nmgp = 8 * nel;
-  if (n < 2 || n > MICRO_NMAX) return;  // (the host refuses these sizes before the launch)
-  const int64_t q = list[blockIdx.x];
-  double* ws = pool + (size_t)slot[q] * MNL_WS * nmgp;
+  if (n < 2 || n > NMAX) return;  // (the host refuses these sizes before the launch)
+  double* const wb = DEV ? wsp + (size_t)blockIdx.x * 6 * ndof : nullptr;
+  double* const su = DEV ? wb : lu;
+  double* const sx = DEV ? wb + ndof : lx;
+  double* const sr = DEV ? wb + 2 * (size_t)ndof : lr;
+  double* const sp = DEV ? wb + 3 * (size_t)ndof : lp;
+  double* const sq = DEV ? wb + 4 * (size_t)ndof : lq;
+  double* const sd = DEV ? wb + 5 * (size_t)ndof : ld;
   const double detJ = 1. / (8. * (double)nel);
   const double Gp[2] = {a.m.E[0] / (2. * (1. + a.m.nu[0])), a.m.E[1] / (2. * (1. + a.m.nu[1]))};
   const double Kp[2] = {a.m.E[0] / (3. * (1. - 2. * a.m.nu[0])), a.m.E[1] / (3. * (1. - 2. * a.m.nu[1]))};
@@ -1222,186 +1249,193 @@ __global__ __launch_bounds__(MICRO_TPB) void k_mnl_solve(MicroNlArgs a, int64_t 
   for (int e = tid; e < nel; e += MICRO_TPB)
     sph[e] = (unsigned char)micro_phase(a.m.type, ne, e % ne, (e / ne) % ne, e / (ne * ne));
   for (int t = tid; t < 8 * 24; t += MICRO_TPB) sdn[t] = mnl_dn(t, ne);
-  {
-    double em[6];
+  // the points of this block: one in the LDS instantiation (one block per listed point)
+  for (int li = blockIdx.x; li < nsolve; li += gridDim.x) {
+    const int64_t q = list[li];
+    double* ws = pool + (size_t)slot[q] * MNL_WS * nmgp;
+    {
+      double em[6];
 #pragma unroll
-    for (int l = 0; l < 6; l++) em[l] = eps[l * ngp + q];
-    const double Eb[3][3] = {{em[0], em[3] / 2., em[4] / 2.}, {em[3] / 2., em[1], em[5] / 2.}, {em[4] / 2., em[5] / 2., em[2]}};
-    mnl_boundary(su, n, Eb);
-  }
-  for (int d = tid; d < ndof; d += MICRO_TPB) sd[d] = 0.;
-  __syncthreads();
+      for (int l = 0; l < 6; l++) em[l] = eps[l * ngp + q];
+      const double Eb[3][3] = {{em[0], em[3] / 2., em[4] / 2.}, {em[3] / 2., em[1], em[5] / 2.}, {em[4] / 2., em[5] / 2., em[2]}};
+      mnl_boundary(su, n, Eb);
+    }
+    for (int d = tid; d < ndof; d += MICRO_TPB) sd[d] = 0.;
+    __syncthreads();
 
-  // one loop, one CG: Newton steps (lc < 0), then the six frozen-tangent load cases lc = 0..5
-  int lc = -1, nits = 0, cgits = 0, status = 0;
-  double nnorm0 = 0., nrel = 0., fmax = -1e300;
-  for (;;) {
-    if (lc < 0) {
-      // state at the iterate su: stresses, new histories and tangent data of every micro point
-      fmax = -1e300;
-      for (int mg = tid; mg < nmgp; mg += MICRO_TPB) {
-        const int e = mg >> 3, gp = mg & 7, ph = sph[e];
-        double ee[6], h[7], s[6], hn[7], nv[6], th, thb;
-        mnl_strain(sdn + 24 * gp, su, n, e % ne, (e / ne) % ne, e / (ne * ne), ee);
+    // one loop, one CG: Newton steps (lc < 0), then the six frozen-tangent load cases lc = 0..5
+    int lc = -1, nits = 0, cgits = 0, status = 0;
+    double nnorm0 = 0., nrel = 0., fmax = -1e300;
+    for (;;) {
+      if (lc < 0) {
+        // state at the iterate su: stresses, new histories and tangent data of every micro point
+        fmax = -1e300;
+        for (int mg = tid; mg < nmgp; mg += MICRO_TPB) {
+          const int e = mg >> 3, gp = mg & 7, ph = sph[e];
+          double ee[6], h[7], s[6], hn[7], nv[6], th, thb;
+          mnl_strain(sdn + 24 * gp, su, n, e % ne, (e / ne) % ne, e / (ne * ne), ee);
 #pragma unroll
-        for (int i = 0; i < 7; i++) h[i] = ws[(size_t)(MNL_H0 + i) * nmgp + mg];
-        const double f = j2_point(ph ? Gp[1] : Gp[0], ph ? Kp[1] : Kp[0], ph ? a.Sy[1] : a.Sy[0],
-                                  ph ? a.Ka[1] : a.Ka[0], ee, h, s, hn, th, thb, nv);
-        fmax = f > fmax ? f : fmax;
+          for (int i = 0; i < 7; i++) h[i] = ws[(size_t)(MNL_H0 + i) * nmgp + mg];
+          const double f = j2_point(ph ? Gp[1] : Gp[0], ph ? Kp[1] : Kp[0], ph ? a.Sy[1] : a.Sy[0],
+                                    ph ? a.Ka[1] : a.Ka[0], ee, h, s, hn, th, thb, nv);
+          fmax = f > fmax ? f : fmax;
 #pragma unroll
-        for (int i = 0; i < 7; i++) ws[(size_t)(MNL_H1 + i) * nmgp + mg] = hn[i];
-        ws[(size_t)MNL_TAN * nmgp + mg] = th;
-        ws[(size_t)(MNL_TAN + 1) * nmgp + mg] = thb;
+          for (int i = 0; i < 7; i++) ws[(size_t)(MNL_H1 + i) * nmgp + mg] = hn[i];
+          ws[(size_t)MNL_TAN * nmgp + mg] = th;
+          ws[(size_t)(MNL_TAN + 1) * nmgp + mg] = thb;
 #pragma unroll
-        for (int b = 0; b < 6; b++) ws[(size_t)(MNL_TAN + 2 + b) * nmgp + mg] = nv[b];
+          for (int b = 0; b < 6; b++) ws[(size_t)(MNL_TAN + 2 + b) * nmgp + mg] = nv[b];
 #pragma unroll
-        for (int k = 0; k < 6; k++) ws[(size_t)(MNL_SIG + k) * nmgp + mg] = s[k];
-      }
-      for (int d = tid; d < ndof; d += MICRO_TPB) sx[d] = 0.;
-      __syncthreads();
-      if (nits == 0) {  // D: the diagonal of K_T at the first iterate, kept for every later solve
-        for (int nd = tid; nd < nn; nd += MICRO_TPB) {
-          const int i = nd % n, j = (nd / n) % n, k = nd / (n * n);
-          if (i == 0 || j == 0 || k == 0 || i == ne || j == ne || k == ne) continue;
-          double dg[3];
-          mnl_diag(ws, sdn, sph, n, i, j, k, detJ, Gp, Kp, dg);
-#pragma unroll
-          for (int r = 0; r < 3; r++) sd[3 * nd + r] = 1. / dg[r];
+          for (int k = 0; k < 6; k++) ws[(size_t)(MNL_SIG + k) * nmgp + mg] = s[k];
         }
+        for (int d = tid; d < ndof; d += MICRO_TPB) sx[d] = 0.;
+        __syncthreads();
+        if (nits == 0) {  // D: the diagonal of K_T at the first iterate, kept for every later solve
+          for (int nd = tid; nd < nn; nd += MICRO_TPB) {
+            const int i = nd % n, j = (nd / n) % n, k = nd / (n * n);
+            if (i == 0 || j == 0 || k == 0 || i == ne || j == ne || k == ne) continue;
+            double dg[3];
+            mnl_diag(ws, sdn, sph, n, i, j, k, detJ, Gp, Kp, dg);
+#pragma unroll
+            for (int r = 0; r < 3; r++) sd[3 * nd + r] = 1. / dg[r];
+          }
+          __syncthreads();
+        }
+      } else {
+        double Eb[3][3];
+        const int p = lc == 5 ? 1 : 0, p2 = lc == 3 ? 1 : 2;  // xy: (0, 1), xz: (0, 2), yz: (1, 2)
+#pragma unroll
+        for (int r = 0; r < 3; r++)
+#pragma unroll
+          for (int d = 0; d < 3; d++)
+            Eb[r][d] = lc < 3 ? ((r == lc && d == lc) ? 1. : 0.) : (((r == p && d == p2) || (r == p2 && d == p)) ? 0.5 : 0.);
+        mnl_boundary(sx, n, Eb);
+        __syncthreads();
+        mnl_apply_tangent(ws, sdn, sph, sx, n, Gp, Kp);
         __syncthreads();
       }
-    } else {
-      double Eb[3][3];
-      const int p = lc == 5 ? 1 : 0, p2 = lc == 3 ? 1 : 2;  // xy: (0, 1), xz: (0, 2), yz: (1, 2)
-#pragma unroll
-      for (int r = 0; r < 3; r++)
-#pragma unroll
-        for (int d = 0; d < 3; d++)
-          Eb[r][d] = lc < 3 ? ((r == lc && d == lc) ? 1. : 0.) : (((r == p && d == p2) || (r == p2 && d == p)) ? 0.5 : 0.);
-      mnl_boundary(sx, n, Eb);
-      __syncthreads();
-      mnl_apply_tangent(ws, sdn, sph, sx, n, Gp, Kp);
-      __syncthreads();
-    }
-    // r = -(internal force) on the interior, p = z = D^-1 r
-    double rz = 0., zz = 0.;
-    for (int nd = tid; nd < nn; nd += MICRO_TPB) {
-      const int i = nd % n, j = (nd / n) % n, k = nd / (n * n);
-      const bool bnd = i == 0 || j == 0 || k == 0 || i == ne || j == ne || k == ne;
-      double y[3] = {0., 0., 0.};
-      if (!bnd) mnl_gather(ws, sdn, n, i, j, k, detJ, y);
-#pragma unroll
-      for (int r = 0; r < 3; r++) {
-        const double rr = bnd ? 0. : -y[r], z = sd[3 * nd + r] * rr;
-        sr[3 * nd + r] = rr;
-        sp[3 * nd + r] = z;
-        sq[3 * nd + r] = 0.;
-        rz += rr * z;
-        zz += z * z;
-      }
-    }
-    micro_reduce2(rz, zz, sred);
-    const double norm0 = sqrt(zz);
-    if (lc < 0) {
-      if (nits == 0) nnorm0 = norm0;
-      nrel = nnorm0 == 0. ? 0. : norm0 / nnorm0;
-      if (nnorm0 == 0. || nrel <= a.nl_rtol) {
-        // converged: the volume average of the micro stresses (the cell's volume is 1), then the tangent
-        double sg[6] = {0., 0., 0., 0., 0., 0.};
-        for (int mg = tid; mg < nmgp; mg += MICRO_TPB)
-#pragma unroll
-          for (int k = 0; k < 6; k++) sg[k] += ws[(size_t)(MNL_SIG + k) * nmgp + mg] * detJ;
-        micro_reduce2(sg[0], sg[1], sred);
-        micro_reduce2(sg[2], sg[3], sred);
-        micro_reduce2(sg[4], sg[5], sred);
-        fmax = mnl_reduce_max(fmax, sred);
-        if (tid == 0) {
-#pragma unroll
-          for (int k = 0; k < 6; k++) sig[k * ngp + q] = sg[k];
-          ftrial[q] = fmax;
-        }
-        lc = 0;
-        continue;
-      }
-      if (nits >= a.nl_max_it) {
-        status = 1;
-        break;
-      }
-    }
-    // Jacobi-CG on K_T,ii x = r from the guess in sx (zero inside)
-    int its = 0, conv = norm0 == 0.;
-    while (!conv && its < a.m.max_it) {
-      mnl_apply_tangent(ws, sdn, sph, sp, n, Gp, Kp);
-      __syncthreads();
-      double pq = 0., dummy = 0.;
+      // r = -(internal force) on the interior, p = z = D^-1 r
+      double rz = 0., zz = 0.;
       for (int nd = tid; nd < nn; nd += MICRO_TPB) {
         const int i = nd % n, j = (nd / n) % n, k = nd / (n * n);
-        if (i == 0 || j == 0 || k == 0 || i == ne || j == ne || k == ne) continue;  // q stays 0
-        double y[3];
-        mnl_gather(ws, sdn, n, i, j, k, detJ, y);
+        const bool bnd = i == 0 || j == 0 || k == 0 || i == ne || j == ne || k == ne;
+        double y[3] = {0., 0., 0.};
+        if (!bnd) mnl_gather(ws, sdn, n, i, j, k, detJ, y);
 #pragma unroll
         for (int r = 0; r < 3; r++) {
-          sq[3 * nd + r] = y[r];
-          pq += sp[3 * nd + r] * y[r];
+          const double rr = bnd ? 0. : -y[r], z = sd[3 * nd + r] * rr;
+          sr[3 * nd + r] = rr;
+          sp[3 * nd + r] = z;
+          sq[3 * nd + r] = 0.;
+          rz += rr * z;
+          zz += z * z;
         }
       }
-      micro_reduce2(pq, dummy, sred);
-      if (!(pq > 0.)) break;  // no curvature left along p: reported as not converged
-      const double alpha = rz / pq;
-      double rz2 = 0., zz2 = 0.;
-      for (int d = tid; d < ndof; d += MICRO_TPB) {
-        sx[d] += alpha * sp[d];
-        const double rr = sr[d] - alpha * sq[d], z = sd[d] * rr;
-        sr[d] = rr;
-        rz2 += rr * z;
-        zz2 += z * z;
+      micro_reduce2(rz, zz, sred);
+      const double norm0 = sqrt(zz);
+      if (lc < 0) {
+        if (nits == 0) nnorm0 = norm0;
+        nrel = nnorm0 == 0. ? 0. : norm0 / nnorm0;
+        if (nnorm0 == 0. || nrel <= a.nl_rtol) {
+          // converged: the volume average of the micro stresses (the cell's volume is 1), then the tangent
+          double sg[6] = {0., 0., 0., 0., 0., 0.};
+          for (int mg = tid; mg < nmgp; mg += MICRO_TPB)
+#pragma unroll
+            for (int k = 0; k < 6; k++) sg[k] += ws[(size_t)(MNL_SIG + k) * nmgp + mg] * detJ;
+          micro_reduce2(sg[0], sg[1], sred);
+          micro_reduce2(sg[2], sg[3], sred);
+          micro_reduce2(sg[4], sg[5], sred);
+          fmax = mnl_reduce_max(fmax, sred);
+          if (tid == 0) {
+#pragma unroll
+            for (int k = 0; k < 6; k++) sig[k * ngp + q] = sg[k];
+            ftrial[q] = fmax;
+          }
+          lc = 0;
+          continue;
+        }
+        if (nits >= a.nl_max_it) {
+          status = 1;
+          break;
+        }
       }
-      micro_reduce2(rz2, zz2, sred);
-      its++;
-      if (sqrt(zz2) / norm0 <= a.m.rtol) {
-        conv = 1;
+      // Jacobi-CG on K_T,ii x = r from the guess in sx (zero inside)
+      int its = 0, conv = norm0 == 0.;
+      while (!conv && its < a.m.max_it) {
+        mnl_apply_tangent(ws, sdn, sph, sp, n, Gp, Kp);
+        __syncthreads();
+        double pq = 0., dummy = 0.;
+        for (int nd = tid; nd < nn; nd += MICRO_TPB) {
+          const int i = nd % n, j = (nd / n) % n, k = nd / (n * n);
+          if (i == 0 || j == 0 || k == 0 || i == ne || j == ne || k == ne) continue;  // q stays 0
+          double y[3];
+          mnl_gather(ws, sdn, n, i, j, k, detJ, y);
+#pragma unroll
+          for (int r = 0; r < 3; r++) {
+            sq[3 * nd + r] = y[r];
+            pq += sp[3 * nd + r] * y[r];
+          }
+        }
+        micro_reduce2(pq, dummy, sred);
+        if (!(pq > 0.)) break;  // no curvature left along p: reported as not converged
+        const double alpha = rz / pq;
+        double rz2 = 0., zz2 = 0.;
+        for (int d = tid; d < ndof; d += MICRO_TPB) {
+          sx[d] += alpha * sp[d];
+          const double rr = sr[d] - alpha * sq[d], z = sd[d] * rr;
+          sr[d] = rr;
+          rz2 += rr * z;
+          zz2 += z * z;
+        }
+        micro_reduce2(rz2, zz2, sred);
+        its++;
+        if (sqrt(zz2) / norm0 <= a.m.rtol) {
+          conv = 1;
+          break;
+        }
+        const double beta = rz2 / rz;
+        rz = rz2;
+        for (int d = tid; d < ndof; d += MICRO_TPB) sp[d] = sd[d] * sr[d] + beta * sp[d];
+        __syncthreads();
+      }
+      __syncthreads();
+      cgits += its;
+      if (!conv) {
+        status = 2;
         break;
       }
-      const double beta = rz2 / rz;
-      rz = rz2;
-      for (int d = tid; d < ndof; d += MICRO_TPB) sp[d] = sd[d] * sr[d] + beta * sp[d];
+      if (lc < 0) {
+        for (int d = tid; d < ndof; d += MICRO_TPB) su[d] += sx[d];
+        nits++;
+        __syncthreads();
+        continue;
+      }
+      // column lc of the tangent: the volume average of C_gp B w
+      mnl_apply_tangent(ws, sdn, sph, sx, n, Gp, Kp);
       __syncthreads();
-    }
-    __syncthreads();
-    cgits += its;
-    if (!conv) {
-      status = 2;
-      break;
-    }
-    if (lc < 0) {
-      for (int d = tid; d < ndof; d += MICRO_TPB) su[d] += sx[d];
-      nits++;
+      double sg[6] = {0., 0., 0., 0., 0., 0.};
+      for (int mg = tid; mg < nmgp; mg += MICRO_TPB)
+#pragma unroll
+        for (int k = 0; k < 6; k++) sg[k] += ws[(size_t)(MNL_SIG + k) * nmgp + mg] * detJ;
+      micro_reduce2(sg[0], sg[1], sred);
+      micro_reduce2(sg[2], sg[3], sred);
+      micro_reduce2(sg[4], sg[5], sred);
+      if (tid == 0)
+#pragma unroll
+        for (int k = 0; k < 6; k++) scol[k * 6 + lc] = sg[k];
       __syncthreads();
-      continue;
+      if (++lc == 6) break;
     }
-    // column lc of the tangent: the volume average of C_gp B w
-    mnl_apply_tangent(ws, sdn, sph, sx, n, Gp, Kp);
-    __syncthreads();
-    double sg[6] = {0., 0., 0., 0., 0., 0.};
-    for (int mg = tid; mg < nmgp; mg += MICRO_TPB)
-#pragma unroll
-      for (int k = 0; k < 6; k++) sg[k] += ws[(size_t)(MNL_SIG + k) * nmgp + mg] * detJ;
-    micro_reduce2(sg[0], sg[1], sred);
-    micro_reduce2(sg[2], sg[3], sred);
-    micro_reduce2(sg[4], sg[5], sred);
-    if (tid == 0)
-#pragma unroll
-      for (int k = 0; k < 6; k++) scol[k * 6 + lc] = sg[k];
-    __syncthreads();
-    if (++lc == 6) break;
-  }
-  if (status == 0 && tid < 36) ctan[tid * ngp + q] = 0.5 * (scol[tid] + scol[(tid % 6) * 6 + tid / 6]);
-  if (tid == 0) {
-    its_out[q] = nits;
-    its_out[ngp + q] = cgits;
-    its_out[2 * ngp + q] = status;
-    rn_out[q] = nrel;
-    if (status) atomicAdd(cnt + 2, 1);
+    if (status == 0 && tid < 36) ctan[tid * ngp + q] = 0.5 * (scol[tid] + scol[(tid % 6) * 6 + tid / 6]);
+    if (tid == 0) {
+      its_out[q] = nits;
+      its_out[ngp + q] = cgits;
+      its_out[2 * ngp + q] = status;
+      rn_out[q] = nrel;
+      if (status) atomicAdd(cnt + 2, 1);
+    }
+    if (!DEV) break;
+    __syncthreads();  // scol and the vectors are read to the end of a point; the next point overwrites them
   }
 }
 
@@ -6397,7 +6431,12 @@ void launch_elastic_ke(Ctx& c) {
 }
 
 void launch_micro_rve(Ctx& c, const MicroArgs& m) {
-  hipLaunchKernelGGL(k_micro_rve, dim3(6), dim3(MICRO_TPB), 0, c.stream, m, c.micro_out, c.mnl_ufield);
+  if (c.micro_mem)
+    hipLaunchKernelGGL(k_micro_rve<true>, dim3(6), dim3(MICRO_TPB), 0, c.stream, m, c.micro_out, c.mnl_ufield,
+                       c.micro_ws);
+  else
+    hipLaunchKernelGGL(k_micro_rve<false>, dim3(6), dim3(MICRO_TPB), 0, c.stream, m, c.micro_out, c.mnl_ufield,
+                       (double*)nullptr);
 }
 
 void launch_mnl_conc(Ctx& c, const MicroNlArgs& a) {
@@ -6415,8 +6454,15 @@ void launch_mnl_linear(Ctx& c, const MicroNlArgs& a) {
 }
 
 void launch_mnl_solve(Ctx& c, const MicroNlArgs& a, int nsolve) {
-  hipLaunchKernelGGL(k_mnl_solve, dim3(nsolve), dim3(MICRO_TPB), 0, c.stream, a, (int64_t)(8 * c.g.nelem), c.mnl_list,
-                     c.mnl_slot, c.eps, c.sig, c.ctan, c.ftrial, c.mnl_pool, c.mnl_its, c.mnl_rn, c.mnl_cnt);
+  const int64_t ngp = 8 * c.g.nelem;
+  if (c.micro_mem)  // at most mnl_ws_blocks workspaces: the blocks walk the list
+    hipLaunchKernelGGL(k_mnl_solve<true>, dim3(std::min(nsolve, c.mnl_ws_blocks)), dim3(MICRO_TPB), 0, c.stream, a, ngp,
+                       c.mnl_list, c.mnl_slot, c.eps, c.sig, c.ctan, c.ftrial, c.mnl_pool, c.mnl_its, c.mnl_rn,
+                       c.mnl_cnt, nsolve, c.mnl_ws);
+  else
+    hipLaunchKernelGGL(k_mnl_solve<false>, dim3(nsolve), dim3(MICRO_TPB), 0, c.stream, a, ngp, c.mnl_list, c.mnl_slot,
+                       c.eps, c.sig, c.ctan, c.ftrial, c.mnl_pool, c.mnl_its, c.mnl_rn, c.mnl_cnt, nsolve,
+                       (double*)nullptr);
 }
 
 void launch_mnl_commit(Ctx& c, const MicroNlArgs& a) {

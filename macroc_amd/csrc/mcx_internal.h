@@ -56,7 +56,9 @@ struct Material {
 };
 
 // -mat_law micro: the two-phase unit cell homogenised on the device (k_micro_rve)
-constexpr int MICRO_NMAX = 10;                                       // nodes per edge (micro_n) supported
+constexpr int MICRO_NMAX = 10;      // nodes per edge (micro_n) with the cell solvers' vectors in LDS (micro_mem 0)
+constexpr int MICRO_NMAX_DEV = 20;  // ... with the vectors in device memory (micro_mem 1): one workgroup
+                                    // per cell still, and the phase bytes (19^3) stay in LDS
 constexpr int MICRO_DOFS = 3 * MICRO_NMAX * MICRO_NMAX * MICRO_NMAX;  // LDS vectors are sized for it
 constexpr int MICRO_TPB = 512;
 constexpr int MICRO_OUT = 16;  // doubles a load case leaves: 6 average stresses, iterations, relative norm, converged
@@ -382,6 +384,15 @@ struct Ctx {
   double* micro_out = nullptr;  // device [6][MICRO_OUT]
   int micro_its[6] = {};
   double micro_rnorm[6] = {};
+  // option micro_mem: 0 the cell solvers' nodal vectors in LDS, 1 in device memory:
+  // k_micro_rve's six workspaces and k_mnl_solve's mnl_ws_blocks workspaces (allocated when first
+  // needed, sized by n; the block count does not grow with the number of points)
+  int micro_mem = 0;
+  double* micro_ws = nullptr;  // [6][5][3 n^3]
+  double* mnl_ws = nullptr;    // [mnl_ws_blocks][6][3 n^3]
+  int64_t micro_ws_bytes = 0, mnl_ws_bytes = 0;
+  int mnl_ws_blocks = 0;       // min(2 x compute units, local Gauss points)
+  int mnl_ws_blocks_opt = 0;   // option micro_mem_blocks (testing the walk): > 0 replaces 2 x compute units
 
   // -mat_law micro_nl: phase Sy / Ka and the Newton settings; the unit-strain fields' strain
   // concentration tensors (with C_hom, after ensure_micro); the slot of every local Gauss point
@@ -394,6 +405,7 @@ struct Ctx {
   int64_t mnl_cap = 0, mnl_used = 0;
   double* mnl_ufield = nullptr;  // [6][3 n^3] unit-strain solutions
   double* mnl_conc = nullptr;    // [MNL_CONC][8 (n-1)^3]
+  int64_t mnl_ufield_bytes = 0, mnl_conc_bytes = 0;  // sized by the cell in use (ensure_micro)
   int* mnl_slot = nullptr;       // [ngp]
   int* mnl_list = nullptr;       // [ngp] points to solve, ascending
   int* mnl_cnt = nullptr;        // [2] new points, points to solve
