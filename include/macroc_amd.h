@@ -287,7 +287,7 @@ int mcx_get_gp_ctan(void* ctx, double* host /* [ngp][36] */);
 
 /* ---- the micro-scale cell (-mat_law micro) ----
  * The unit cube with micro_n nodes per edge (2 <= micro_n <= 10; <= 20 with the option "micro_mem" 1,
- * below), ne = micro_n - 1 Q1 hexahedra per
+ * <= 128 with the option "micro_solver" 1, both below), ne = micro_n - 1 Q1 hexahedra per
  * edge, 2x2x2 Gauss points, physical B.  Material 0 is micro_mat_1, material 1 micro_mat_2 (E, nu;
  * isotropic elastic, Sy and Ka unused).  Element (i, j, k), 0 <= i, j, k < ne, is of material 1 iff
  *   micro_type 0 (centred sphere, radius 0.5): (2i+1-ne)^2 + (2j+1-ne)^2 + (2k+1-ne)^2 < ne^2
@@ -306,7 +306,17 @@ int mcx_get_gp_ctan(void* ctx, double* host /* [ngp][36] */);
  * workspace (six of 5 x 3 micro_n^3 doubles here; for -mat_law micro_nl min(2 x compute units,
  * local Gauss points) of 6 x 3 micro_n^3 doubles, whatever the number of solved points) and
  * accepts micro_n <= 20.  For micro_n <= 10 both give the same bits.  The option recomputes C_hom
- * and is refused while history slots of -mat_law micro_nl are in use. */
+ * and is refused while history slots of -mat_law micro_nl are in use.
+ * "micro_solver" (mcx_set_option; -micro_solver cell|grid through mcx_apply_args): 0 (default) solves
+ * each load case in one workgroup, with the limits above; 1 spreads every load case over the whole
+ * device, one workgroup per tile of 8x8x8 nodes and one kernel launch per CG phase, and accepts
+ * 2 <= micro_n <= 128 (-mat_law micro only: a -mat_law micro_nl context refuses it with code 2; on
+ * other contexts it has no effect).  Its workspace, 6 x 5 x 3 micro_n^3 doubles plus a few partial
+ * sums, is counted in device_bytes and freed when the option returns to 0; "micro_mem" is ignored.
+ * The definition is the same; the dot products are summed in another order, so C_hom agrees with
+ * solver 0's to the CG's tolerance, not bit for bit.  Two runs give the same bits.
+ * "micro_grid_poll" (1 .. 4096, default 16): the CG iterations solver 1 enqueues between two host
+ * reads of the load cases' done flags; a tuning knob, the results do not depend on it. */
 /* C_hom (row major, C[k*6+l]) and, per load case, the CG iterations and the final relative
    preconditioned residual norm.  Any pointer may be NULL. */
 int mcx_micro_get_ctan(void* ctx, double C[36], int its[6], double rnorm[6]);
@@ -399,14 +409,14 @@ int mcx_set_timing(void* ctx, int on);
 int mcx_get_timing(void* ctx, mcx_timing* t);
 int mcx_synchronize(void* ctx);
 /* tuning knobs ("spmv_subl": lines per sub-slab of the SpMV sweep, 0 = whole XCD slab; "micro_rtol",
-   "micro_max_it", "micro_mem": the micro cell's CG, -mat_law micro; "micro_nl_rtol", "micro_nl_max_it", "micro_nl_slots":
+   "micro_max_it", "micro_mem", "micro_solver", "micro_grid_poll": the micro cell's CG, -mat_law micro; "micro_nl_rtol", "micro_nl_max_it", "micro_nl_slots":
    -mat_law micro_nl) and a
    device-only SpMV timer (iters launches on the current search direction, HIP events) */
 int mcx_set_option(void* ctx, const char* name, double value);
 /* the command-line flags that have no mcx_opts field, applied to a context through mcx_set_option:
-   -micro_mem lds|device ("micro_mem" 0 | 1), -micro_rtol, -micro_max_it, -micro_nl_rtol,
-   -micro_nl_max_it, -micro_nl_slots (each with a number).  mcx_parse_args accepts these flags and
-   checks -micro_mem's word; call this after mcx_init with the same argv.  Other flags are skipped. */
+   -micro_mem lds|device ("micro_mem" 0 | 1), -micro_solver cell|grid ("micro_solver" 0 | 1),
+   -micro_rtol, -micro_max_it, -micro_nl_rtol, -micro_nl_max_it, -micro_nl_slots (each with a
+   number).  mcx_parse_args accepts these flags and checks -micro_mem's and -micro_solver's word; call this after mcx_init with the same argv.  Other flags are skipped. */
 int mcx_apply_args(void* ctx, int argc, const char* const* argv);
 int mcx_time_spmv(void* ctx, int iters, double* avg_ms);
 

@@ -99,7 +99,7 @@ static int free_ctx(Ctx* c) {
   if (c->comm_stream) (void)hipStreamSynchronize(c->comm_stream);
   if (c->x_stream) (void)hipStreamSynchronize(c->x_stream);
   if (c->f_stream) (void)hipStreamSynchronize(c->f_stream);
-  void* ptrs[] = {c->micro_out, c->micro_ws, c->mnl_ws, c->mnl_ufield, c->mnl_conc, c->mnl_slot, c->mnl_list, c->mnl_cnt, c->mnl_its, c->mnl_rn, c->mnl_pool, c->hist_old, c->hist_new, c->ftrial, c->b, c->du, c->r, c->z, c->w, c->jix, c->jdd, c->V, c->U, c->D, c->d_mask, c->vi_idx, c->wd, c->vi_dict, c->vi_keys, c->vi_slot, c->vi_ctl, c->vi_bdict, c->eps, c->sig, c->ctan, c->Ke,
+  void* ptrs[] = {c->micro_out, c->micro_ws, c->micro_grid_ws, c->mnl_ws, c->mnl_ufield, c->mnl_conc, c->mnl_slot, c->mnl_list, c->mnl_cnt, c->mnl_its, c->mnl_rn, c->mnl_pool, c->hist_old, c->hist_new, c->ftrial, c->b, c->du, c->r, c->z, c->w, c->jix, c->jdd, c->V, c->U, c->D, c->d_mask, c->vi_idx, c->wd, c->vi_dict, c->vi_keys, c->vi_slot, c->vi_ctl, c->vi_bdict, c->eps, c->sig, c->ctan, c->Ke,
                   c->vib_keys, c->vib_ctl, c->vib_pos, c->ke_uni, c->xdone, c->esc_node, c->esc_res, c->esc_slot, c->elem_plain, c->cref, c->vi_xslot,
                   c->vi_xlist, c->vi_xcnt, c->vi_exc, c->st_coef, c->st_ids, c->st_slot, c->st_list, c->st_cnt, c->st_mask,
                   c->partials, c->red, c->red_loc, c->cg, c->hist, c->tmp, c->halo.d_send_idx,
@@ -385,8 +385,8 @@ using namespace mcx;
 
 // command-line flags that are options of a context (mcx_set_option names behind a '-'), not
 // mcx_opts fields: mcx_parse_args accepts them, mcx_apply_args applies them after mcx_init
-static const char* const kApplyFlags[] = {"-micro_mem",     "-micro_rtol",      "-micro_max_it",
-                                          "-micro_nl_rtol", "-micro_nl_max_it", "-micro_nl_slots"};
+static const char* const kApplyFlags[] = {"-micro_mem",     "-micro_rtol",      "-micro_max_it",  "-micro_nl_rtol",
+                                          "-micro_nl_max_it", "-micro_nl_slots", "-micro_solver"};
 static bool apply_flag(const char* k) {
   for (const char* f : kApplyFlags)
     if (!std::strcmp(k, f)) return true;
@@ -514,6 +514,10 @@ int mcx_parse_args(mcx_opts* o, int argc, const char* const* argv) try {
     if (apply_flag(k)) {  // options of the context: mcx_apply_args sets them after mcx_init
       if (!std::strcmp(k, "-micro_mem") && (!v || (std::strcmp(v, "lds") && std::strcmp(v, "device")))) {
         set_error(std::string("-micro_mem: lds or device, got ") + (v ? v : "(none)"));
+        return 2;
+      }
+      if (!std::strcmp(k, "-micro_solver") && (!v || (std::strcmp(v, "cell") && std::strcmp(v, "grid")))) {
+        set_error(std::string("-micro_solver: cell or grid, got ") + (v ? v : "(none)"));
         return 2;
       }
       a++;
@@ -817,15 +821,22 @@ static MicroNlArgs mnl_args(const Ctx& c) {
   return a;
 }
 
-// the largest micro_n of the memory mode in use (option micro_mem)
-static int micro_nmax(const Ctx& c) { return c.micro_mem ? MICRO_NMAX_DEV : MICRO_NMAX; }
+// the grid-wide solver (option micro_solver 1) serves -mat_law micro only
+static bool micro_grid(const Ctx& c) { return c.micro_solver == 1 && c.mat.law == MCX_LAW_MICRO; }
+
+// the largest micro_n of the solver and memory mode in use (options micro_solver, micro_mem)
+static int micro_nmax(const Ctx& c) {
+  return micro_grid(c) ? MICRO_NMAX_GRID : c.micro_mem ? MICRO_NMAX_DEV : MICRO_NMAX;
+}
 
 static int micro_n_refused(const Ctx& c) {
   const int n = c.micro.n;
   if (n >= 2 && n <= micro_nmax(c)) return 0;
   std::string e = "-mat_law micro: -micro_n " + std::to_string(n) + " outside the supported range 2 <= micro_n <= " +
                   std::to_string(micro_nmax(c));
-  if (c.micro_mem)
+  if (micro_grid(c))
+    e += " (option micro_solver 1: one workgroup per tile of 8x8x8 nodes, the CG state in device memory)";
+  else if (c.micro_mem)
     e += " (option micro_mem 1: one workgroup per cell with its CG state in device memory)";
   else
     e += " (option micro_mem 0: the cell's CG state has to fit one CU's LDS; micro_mem 1 / -micro_mem device keeps "
@@ -851,6 +862,29 @@ static int micro_resize(Ctx& c, double** p, int64_t* bytes, int64_t want) {
   return 0;
 }
 
+// option micro_solver 1: the six solves as launches over the whole device.  The host
+// enqueues micro_grid_poll gated iterations at a time and reads the six done flags back; the
+// device stops every load case by itself (converged, !(pq > 0), max_it), so what is enqueued past
+// that changes nothing and the results do not depend on micro_grid_poll.
+static int solve_micro_grid(Ctx& c, const MicroArgs& m) {
+  if (int rc = micro_resize(c, &c.micro_grid_ws, &c.micro_grid_bytes, mg_ws_bytes(m.n))) return rc;
+  const MicroGridWs w = mg_layout(c.micro_grid_ws, m.n);
+  launch_mg_setup(c, m, w);
+  MCX_HIP(hipGetLastError());
+  for (int64_t enq = 0;;) {
+    MicroGridState h[6];
+    MCX_HIP(hipMemcpyAsync(h, w.st, sizeof(h), hipMemcpyDeviceToHost, c.stream));
+    MCX_HIP(hipStreamSynchronize(c.stream));
+    bool done = true;
+    for (int l = 0; l < 6; l++) done = done && h[l].done;
+    if (done || enq >= m.max_it) break;
+    for (int q = 0; q < c.micro_grid_poll && enq < m.max_it; q++, enq++) launch_mg_iterate(c, m, w);
+    MCX_HIP(hipGetLastError());
+  }
+  launch_mg_finish(c, m, w);
+  return 0;
+}
+
 static int ensure_micro(Ctx& c) {
   if (!micro_law(c.mat.law) || !c.micro_dirty) return 0;
   MicroArgs m = c.micro;
@@ -869,9 +903,14 @@ static int ensure_micro(Ctx& c) {
         (rc = micro_resize(c, &c.mnl_conc, &c.mnl_conc_bytes, (int64_t)sizeof(double) * MNL_CONC * nmgp)))
       return rc;
   }
-  const int64_t rve_ws = c.micro_mem ? (int64_t)sizeof(double) * 6 * 5 * ndof : 0;  // micro_mem 1: six workspaces
-  if (int rc = micro_resize(c, &c.micro_ws, &c.micro_ws_bytes, rve_ws)) return rc;
-  launch_micro_rve(c, m);
+  if (micro_grid(c)) {  // the same six results in micro_out, by the grid-wide solver
+    if (int rc = micro_resize(c, &c.micro_ws, &c.micro_ws_bytes, 0)) return rc;
+    if (int rc = solve_micro_grid(c, m)) return rc;
+  } else {
+    const int64_t rve_ws = c.micro_mem ? (int64_t)sizeof(double) * 6 * 5 * ndof : 0;  // micro_mem 1: six workspaces
+    if (int rc = micro_resize(c, &c.micro_ws, &c.micro_ws_bytes, rve_ws)) return rc;
+    launch_micro_rve(c, m);
+  }
   MCX_HIP(hipGetLastError());
   double h[6 * MICRO_OUT];
   MCX_HIP(hipMemcpyAsync(h, c.micro_out, sizeof(h), hipMemcpyDeviceToHost, c.stream));
@@ -1953,6 +1992,32 @@ int mcx_set_option(void* ctx, const char* name, double value) try {
     c.micro_dirty = true;  // C_hom and the concentration tensors are recomputed, the workspaces resized
     return 0;
   }
+  if (!std::strcmp(name, "micro_solver")) {  // who solves the six unit-strain problems of -mat_law micro
+    if (value != 0. && value != 1.) {
+      set_error("micro_solver: 0 (one workgroup per load case, micro_n <= " + std::to_string(MICRO_NMAX) + " / " +
+                std::to_string(MICRO_NMAX_DEV) + " by micro_mem) or 1 (grid-wide, one workgroup per tile, micro_n <= " +
+                std::to_string(MICRO_NMAX_GRID) + ")");
+      return 1;
+    }
+    if ((int)value == c.micro_solver) return 0;
+    if (value == 1. && c.mat.law == MCX_LAW_MICRO_NL) {
+      set_error("micro_solver 1: not with -mat_law micro_nl (its linear shortcut needs the unit-strain fields and its "
+                "per-point solver ends at micro_n " + std::to_string(MICRO_NMAX_DEV) + ")");
+      return 2;
+    }
+    c.micro_solver = (int)value;
+    c.micro_dirty = true;  // C_hom is recomputed by the other solver
+    if (!c.micro_solver) return micro_resize(c, &c.micro_grid_ws, &c.micro_grid_bytes, 0);
+    return 0;
+  }
+  if (!std::strcmp(name, "micro_grid_poll")) {  // tuning / testing: CG iterations enqueued between two host polls
+    if (!(value >= 1.) || value > 4096. || value != (double)(int)value) {
+      set_error("micro_grid_poll: an integer 1 .. 4096");
+      return 1;
+    }
+    c.micro_grid_poll = (int)value;
+    return 0;
+  }
   if (!std::strcmp(name, "spmv_subl")) {
     const int old = c.spmv_subl;
     c.spmv_subl = (int)value;
@@ -2347,6 +2412,12 @@ int mcx_apply_args(void* ctx, int argc, const char* const* argv) try {
         return 2;
       }
       value = std::strcmp(v, "device") ? 0. : 1.;
+    } else if (!std::strcmp(k, "-micro_solver")) {
+      if (std::strcmp(v, "cell") && std::strcmp(v, "grid")) {
+        set_error(std::string("-micro_solver: cell or grid, got ") + v);
+        return 2;
+      }
+      value = std::strcmp(v, "grid") ? 0. : 1.;
     } else {
       value = std::atof(v);
     }

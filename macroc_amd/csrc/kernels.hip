@@ -1448,6 +1448,354 @@ __global__ __launch_bounds__(TPB) void k_mnl_commit(double* __restrict__ pool, i
   ws[t % nh] = ws[nh + t % nh];
 }
 
+// ---------------------------------------------------------------------------- grid-wide micro cell
+// option micro_solver 1: k_micro_rve's six unit-strain solves, statement for statement,
+// with every cell spread over the device: one workgroup per tile of MG_T^3 nodes of one load case
+// (blockIdx.x = tile, blockIdx.y = load case), the five vectors in device memory, and one kernel
+// launch per CG phase, so that kernel boundaries on the stream are the only ordering between
+// workgroups: nothing waits, spins or uses an atomic.  Every kernel of an iteration first reads its
+// load case's done flag and returns when it is set, so iterations enqueued past the end change
+// nothing.  The element matrices, the boundary values, the inverse diagonal and a row of K p are
+// the bits k_micro_rve computes from the same inputs; the dot products are summed tile by tile
+// (wave butterfly, wave sums ascending, then the tiles' partials strided over 512 threads and the
+// same tree again), an order that depends on n alone.
+__device__ __forceinline__ double* mg_vec(const MicroGridWs& w, int lc, int v, int64_t ndof) {
+  return w.vec + ((size_t)lc * 5 + v) * (size_t)ndof;  // v: 0 x, 1 r, 2 p, 3 q, 4 D^-1
+}
+__device__ __forceinline__ double* mg_part(const MicroGridWs& w, int lc, int q) {
+  return w.part + ((size_t)lc * MG_NPART + q) * (size_t)w.npart;
+}
+
+// the two phases' element matrices (k_micro_rve's statements), once per solve
+__global__ __launch_bounds__(MICRO_TPB) void k_mg_ke(MicroArgs m, MicroGridWs w) {
+  __shared__ double sdn[8 * 24];
+  const int tid = threadIdx.x, ne = m.n - 1, nel = ne * ne * ne;
+  const double detJ = 1. / (8. * (double)nel);
+  for (int t = tid; t < 8 * 24; t += MICRO_TPB) sdn[t] = mnl_dn(t, ne);
+  __syncthreads();
+  for (int t = tid; t < 2 * 576; t += MICRO_TPB) {
+    const int ph = t / 576, i = (t % 576) / 24, j = t % 24;
+    double s = 0.;
+#pragma unroll 1
+    for (int gp = 0; gp < 8; gp++)
+#pragma unroll 1
+      for (int k = 0; k < 6; k++) {
+        const double bk = micro_B(sdn + 24 * gp, k, i / 3, i % 3);
+        if (bk == 0.) continue;
+#pragma unroll 1
+        for (int l = 0; l < 6; l++)
+          s += bk * micro_iso_C(ph ? m.E[1] : m.E[0], ph ? m.nu[1] : m.nu[0], k, l) * micro_B(sdn + 24 * gp, l, j / 3, j % 3) * detJ;
+      }
+    w.ske[t] = s;
+  }
+}
+
+// u = E_l x on the boundary, 0 inside; the Jacobi inverse diagonal of the interior dofs: one thread per node
+__global__ __launch_bounds__(MICRO_TPB) void k_mg_init(MicroArgs m, MicroGridWs w) {
+  const int lc = blockIdx.y, n = m.n, ne = n - 1, nn = n * n * n;
+  const int nd = blockIdx.x * MICRO_TPB + threadIdx.x;
+  if (nd >= nn) return;
+  const int64_t ndof = 3 * (int64_t)nn;
+  double* const sx = mg_vec(w, lc, 0, ndof);
+  double* const sd = mg_vec(w, lc, 4, ndof);
+  const int i = nd % n, j = (nd / n) % n, k = nd / (n * n);
+  const bool bnd = i == 0 || j == 0 || k == 0 || i == ne || j == ne || k == ne;
+  const double X[3] = {(double)i / (double)ne, (double)j / (double)ne, (double)k / (double)ne};
+  double u[3] = {0., 0., 0.};
+  if (bnd) {
+    const int p = lc == 5 ? 1 : 0, q = lc == 3 ? 1 : 2;
+#pragma unroll
+    for (int r = 0; r < 3; r++)
+#pragma unroll
+      for (int d = 0; d < 3; d++) {
+        const double e = lc < 3 ? ((r == lc && d == lc) ? 1. : 0.) : (((r == p && d == q) || (r == q && d == p)) ? 0.5 : 0.);
+        if (e != 0.) u[r] = e * X[d];
+      }
+  }
+  double dg[3] = {0., 0., 0.};
+#pragma unroll 1
+  for (int oz = 1; oz >= 0; oz--)
+#pragma unroll 1
+    for (int oy = 1; oy >= 0; oy--)
+#pragma unroll 1
+      for (int ox = 1; ox >= 0; ox--) {
+        const int ei = i - ox, ej = j - oy, ek = k - oz;
+        if (ei < 0 || ej < 0 || ek < 0 || ei >= ne || ej >= ne || ek >= ne) continue;
+        const int a = ox + 2 * oy + 4 * oz;
+        const double* ke = w.ske + 576 * micro_phase(m.type, ne, ei, ej, ek);
+#pragma unroll
+        for (int r = 0; r < 3; r++) dg[r] += ke[(3 * a + r) * 25];
+      }
+#pragma unroll
+  for (int r = 0; r < 3; r++) {
+    sx[3 * (size_t)nd + r] = u[r];
+    sd[3 * (size_t)nd + r] = bnd ? 0. : 1. / dg[r];
+  }
+}
+
+// The operator.  The workgroup stages its tile's halo of the source vector (MG_H^3 nodes,
+// component-major: a 32-lane group's 8-byte reads of one component are four tile rows of 8
+// consecutive doubles, MG_H apart, so only the fourth row's first 6 lanes meet the first row's
+// banks again), the two element matrices and the (MG_T + 1)^3 phase bytes of the elements its nodes touch, then a
+// thread gathers its node's row with micro_apply's loop nest.  INIT: the source is x and the
+// epilogue is r = -(K x), p = z = D^-1 r, q = 0 with the tile's r.z and z.z; else the source is p,
+// q = K p on the interior nodes (boundary rows of q stay 0 from INIT) with the tile's p.q.
+// one element's share of a node's row: micro_apply's innermost loops on the staged halo; ei, ej, ek
+// = the element's node 0 in halo coordinates, row = the 3 x 24 rows of the node in the element's
+// matrix.  UNI: row is the same address in every lane (global memory), the loop is unrolled so that
+// the 72 entries arrive by scalar loads; else row points into LDS.  The same products and sums.
+template <bool UNI>
+__device__ __forceinline__ void mg_elem(const double* __restrict__ row, const double* __restrict__ sv, int ei, int ej,
+                                        int ek, double (&y)[3]) {
+  constexpr int H3 = MG_H * MG_H * MG_H;
+#pragma unroll(UNI ? 8 : 1)
+  for (int b = 0; b < 8; b++) {
+    const int hb = (ei + (b & 1)) + MG_H * ((ej + (b >> 1 & 1)) + MG_H * (ek + (b >> 2)));
+    const double v0 = sv[hb], v1 = sv[H3 + hb], v2 = sv[2 * H3 + hb];
+#pragma unroll
+    for (int r = 0; r < 3; r++) {
+      const double* kr = row + 24 * r + 3 * b;
+      y[r] += kr[0] * v0;
+      y[r] += kr[1] * v1;
+      y[r] += kr[2] * v2;
+    }
+  }
+}
+
+template <bool INIT>
+__global__ __launch_bounds__(MICRO_TPB) void k_mg_apply(MicroArgs m, MicroGridWs w) {
+  constexpr int H3 = MG_H * MG_H * MG_H, E1 = MG_T + 1;
+  __shared__ double sv[3 * H3];
+  __shared__ double ske[2 * 576];
+  __shared__ double sred[2 * (MICRO_TPB / 64)];
+  __shared__ unsigned char sph[E1 * E1 * E1];
+  const int tid = threadIdx.x, lc = blockIdx.y;
+  if (!INIT && w.st[lc].done) return;  // the same for the whole workgroup
+  const int n = m.n, ne = n - 1, nt = w.ntile, tile = blockIdx.x;
+  const int64_t ndof = 3 * (int64_t)n * n * n;
+  const int ox = MG_T * (tile % nt), oy = MG_T * ((tile / nt) % nt), oz = MG_T * (tile / (nt * nt));
+  const double* const src = mg_vec(w, lc, INIT ? 0 : 2, ndof);
+  for (int t = tid; t < 2 * 576; t += MICRO_TPB) ske[t] = w.ske[t];
+  for (int e = tid; e < E1 * E1 * E1; e += MICRO_TPB) {
+    const int ei = ox - 1 + e % E1, ej = oy - 1 + (e / E1) % E1, ek = oz - 1 + e / (E1 * E1);
+    const bool in = ei >= 0 && ej >= 0 && ek >= 0 && ei < ne && ej < ne && ek < ne;
+    sph[e] = in ? (unsigned char)micro_phase(m.type, ne, ei, ej, ek) : (unsigned char)0;
+  }
+  for (int h = tid; h < H3; h += MICRO_TPB) {
+    const int gi = ox - 1 + h % MG_H, gj = oy - 1 + (h / MG_H) % MG_H, gk = oz - 1 + h / (MG_H * MG_H);
+    const bool in = gi >= 0 && gj >= 0 && gk >= 0 && gi < n && gj < n && gk < n;
+    const size_t nd = in ? (size_t)gi + (size_t)n * ((size_t)gj + (size_t)n * (size_t)gk) : 0;
+#pragma unroll
+    for (int r = 0; r < 3; r++) sv[r * H3 + h] = in ? src[3 * nd + r] : 0.;
+  }
+  __syncthreads();
+  const int li = tid % MG_T, lj = (tid / MG_T) % MG_T, lk = tid / (MG_T * MG_T);
+  const int i = ox + li, j = oy + lj, k = oz + lk;
+  const bool in = i < n && j < n && k < n;  // the cell's upper tiles are partial
+  const bool bnd = i == 0 || j == 0 || k == 0 || i == ne || j == ne || k == ne;
+  const size_t nd = in ? (size_t)i + (size_t)n * ((size_t)j + (size_t)n * (size_t)k) : 0;
+  double y[3] = {0., 0., 0.};
+  if (in && !bnd) {  // all 8 elements of an interior node exist; micro_apply's order
+#pragma unroll 1
+    for (int dz = 1; dz >= 0; dz--)
+#pragma unroll 1
+      for (int dy = 1; dy >= 0; dy--)
+#pragma unroll 1
+        for (int dx = 1; dx >= 0; dx--) {
+          const int ei = li + 1 - dx, ej = lj + 1 - dy, ek = lk + 1 - dz;  // element and its node 0 in halo coordinates
+          const int a = dx + 2 * dy + 4 * dz;
+          const int ph = sph[ei + E1 * (ej + E1 * ek)];
+          const int ph0 = __builtin_amdgcn_readfirstlane(ph);
+          if (__all(ph == ph0))  // the wave's elements share a phase: their matrix rows through the scalar cache
+            mg_elem<true>(w.ske + 576 * ph0 + 72 * a, sv, ei, ej, ek, y);
+          else
+            mg_elem<false>(ske + 576 * ph + 72 * a, sv, ei, ej, ek, y);
+        }
+  }
+  double s0 = 0., s1 = 0.;
+  if (INIT) {
+    if (in) {
+      double* const sr = mg_vec(w, lc, 1, ndof);
+      double* const sp = mg_vec(w, lc, 2, ndof);
+      double* const sq = mg_vec(w, lc, 3, ndof);
+      const double* const sd = mg_vec(w, lc, 4, ndof);
+#pragma unroll
+      for (int r = 0; r < 3; r++) {
+        const double rr = bnd ? 0. : -y[r], z = sd[3 * nd + r] * rr;
+        sr[3 * nd + r] = rr;
+        sp[3 * nd + r] = z;
+        sq[3 * nd + r] = 0.;
+        s0 += rr * z;
+        s1 += z * z;
+      }
+    }
+  } else if (in && !bnd) {
+    double* const sq = mg_vec(w, lc, 3, ndof);
+    const int hc = (li + 1) + MG_H * ((lj + 1) + MG_H * (lk + 1));
+#pragma unroll
+    for (int r = 0; r < 3; r++) {
+      sq[3 * nd + r] = y[r];
+      s0 += sv[r * H3 + hc] * y[r];
+    }
+  }
+  micro_reduce2(s0, s1, sred);
+  if (tid == 0) {
+    mg_part(w, lc, 0)[tile] = s0;
+    if (INIT) mg_part(w, lc, 1)[tile] = s1;
+  }
+}
+
+// The scalar steps, one workgroup per load case: the partials in ascending order strided over the
+// threads, then micro_reduce2's tree; thread 0 writes the state record.
+//   PHASE 0  after the INIT apply: norm0, rz; converged at once when the first norm is 0
+//   PHASE 1  after q = K p: pq, alpha; !(pq > 0) ends the solve unconverged
+//   PHASE 2  after the x / r update: the iteration count, rel, converged or beta and the new rz
+template <int PHASE>
+__global__ __launch_bounds__(MICRO_TPB) void k_mg_scalar(MicroArgs m, MicroGridWs w, int cnt) {
+  __shared__ double sred[2 * (MICRO_TPB / 64)];
+  const int tid = threadIdx.x, lc = blockIdx.x;
+  MicroGridState& st = w.st[lc];
+  if (PHASE != 0 && st.done) return;
+  const double* const p0 = mg_part(w, lc, 0);
+  const double* const p1 = mg_part(w, lc, 1);
+  double a = 0., b = 0.;
+  for (int q = tid; q < cnt; q += MICRO_TPB) {
+    a += p0[q];
+    if (PHASE != 1) b += p1[q];
+  }
+  micro_reduce2(a, b, sred);
+  if (tid != 0) return;
+  if (PHASE == 0) {
+    st.rz = a;
+    st.norm0 = sqrt(b);
+    st.pq = st.alpha = st.beta = st.rel = 0.;
+    st.its = 0;
+    st.conv = st.norm0 == 0.;  // n = 2 (no interior dof) or a load case the zero guess solves
+    st.done = st.conv || !(0 < m.max_it);
+    st.pad = 0;
+  } else if (PHASE == 1) {
+    st.pq = a;
+    if (!(a > 0.))
+      st.done = 1;  // no curvature left along p: reported as not converged
+    else
+      st.alpha = st.rz / a;
+  } else {
+    st.its++;
+    st.rel = sqrt(b) / st.norm0;
+    if (st.rel <= m.rtol) {
+      st.conv = 1;
+      st.done = 1;
+    } else {
+      st.beta = a / st.rz;
+      st.rz = a;
+      if (!(st.its < m.max_it)) st.done = 1;
+    }
+  }
+}
+
+// x += alpha p, r -= alpha q, z = D^-1 r: one thread per dof, the block's r.z and z.z
+__global__ __launch_bounds__(MICRO_TPB) void k_mg_update(MicroArgs m, MicroGridWs w) {
+  __shared__ double sred[2 * (MICRO_TPB / 64)];
+  const int lc = blockIdx.y;
+  if (w.st[lc].done) return;
+  const int64_t ndof = 3 * (int64_t)m.n * m.n * m.n, d = (int64_t)blockIdx.x * MICRO_TPB + threadIdx.x;
+  const double alpha = w.st[lc].alpha;
+  double rz = 0., zz = 0.;
+  if (d < ndof) {
+    double* const sx = mg_vec(w, lc, 0, ndof);
+    double* const sr = mg_vec(w, lc, 1, ndof);
+    sx[d] += alpha * mg_vec(w, lc, 2, ndof)[d];
+    const double rr = sr[d] - alpha * mg_vec(w, lc, 3, ndof)[d], z = mg_vec(w, lc, 4, ndof)[d] * rr;
+    sr[d] = rr;
+    rz += rr * z;
+    zz += z * z;
+  }
+  micro_reduce2(rz, zz, sred);
+  if (threadIdx.x == 0) {
+    mg_part(w, lc, 0)[blockIdx.x] = rz;
+    mg_part(w, lc, 1)[blockIdx.x] = zz;
+  }
+}
+
+// p = z + beta p
+__global__ __launch_bounds__(MICRO_TPB) void k_mg_pupdate(MicroArgs m, MicroGridWs w) {
+  const int lc = blockIdx.y;
+  if (w.st[lc].done) return;
+  const int64_t ndof = 3 * (int64_t)m.n * m.n * m.n, d = (int64_t)blockIdx.x * MICRO_TPB + threadIdx.x;
+  if (d >= ndof) return;
+  double* const sp = mg_vec(w, lc, 2, ndof);
+  sp[d] = mg_vec(w, lc, 4, ndof)[d] * mg_vec(w, lc, 1, ndof)[d] + w.st[lc].beta * sp[d];
+}
+
+// volume average of the Gauss-point stresses: one thread per element (the tile of its lowest node),
+// k_micro_rve's Gauss-point loop, the tile's six partial sums
+__global__ __launch_bounds__(MICRO_TPB) void k_mg_stress(MicroArgs m, MicroGridWs w) {
+  __shared__ double sdn[8 * 24];
+  __shared__ double sred[2 * (MICRO_TPB / 64)];
+  const int tid = threadIdx.x, lc = blockIdx.y, tile = blockIdx.x;
+  const int n = m.n, ne = n - 1, nel = ne * ne * ne, nt = w.ntile;
+  const int64_t ndof = 3 * (int64_t)n * n * n;
+  const double detJ = 1. / (8. * (double)nel);
+  const double* const sx = mg_vec(w, lc, 0, ndof);
+  for (int t = tid; t < 8 * 24; t += MICRO_TPB) sdn[t] = mnl_dn(t, ne);
+  __syncthreads();
+  const int ei = MG_T * (tile % nt) + tid % MG_T, ej = MG_T * ((tile / nt) % nt) + (tid / MG_T) % MG_T,
+            ek = MG_T * (tile / (nt * nt)) + tid / (MG_T * MG_T);
+  double sg[6] = {0., 0., 0., 0., 0., 0.};
+  if (ei < ne && ej < ne && ek < ne) {
+    const int ph = micro_phase(m.type, ne, ei, ej, ek);
+    const double Ee = ph ? m.E[1] : m.E[0], nue = ph ? m.nu[1] : m.nu[0];
+#pragma unroll 1
+    for (int gp = 0; gp < 8; gp++) {
+      const double* dn = sdn + 24 * gp;
+      double G[3][3] = {{0., 0., 0.}, {0., 0., 0.}, {0., 0., 0.}};  // G[r][d] = d u_r / d x_d
+#pragma unroll 1
+      for (int a = 0; a < 8; a++) {
+        const size_t nb = (size_t)(ei + (a & 1)) + (size_t)n * ((size_t)(ej + (a >> 1 & 1)) + (size_t)n * (size_t)(ek + (a >> 2)));
+#pragma unroll
+        for (int r = 0; r < 3; r++)
+#pragma unroll
+          for (int d = 0; d < 3; d++) G[r][d] += dn[3 * a + d] * sx[3 * nb + r];
+      }
+      const double eps[6] = {G[0][0], G[1][1], G[2][2], G[0][1] + G[1][0], G[0][2] + G[2][0], G[1][2] + G[2][1]};
+#pragma unroll
+      for (int k = 0; k < 6; k++) {
+        double s = 0.;
+#pragma unroll
+        for (int l = 0; l < 6; l++) s += micro_iso_C(Ee, nue, k, l) * eps[l];
+        sg[k] += s * detJ;
+      }
+    }
+  }
+  micro_reduce2(sg[0], sg[1], sred);
+  micro_reduce2(sg[2], sg[3], sred);
+  micro_reduce2(sg[4], sg[5], sred);
+  if (tid == 0)
+    for (int k = 0; k < 6; k++) mg_part(w, lc, k)[tile] = sg[k];
+}
+
+// the tiles' stress partials in the scalar steps' fixed order, and the state, in k_micro_rve's layout
+__global__ __launch_bounds__(MICRO_TPB) void k_mg_out(MicroGridWs w, int cnt, double* __restrict__ out) {
+  __shared__ double sred[2 * (MICRO_TPB / 64)];
+  const int tid = threadIdx.x, lc = blockIdx.x;
+  double sg[6] = {0., 0., 0., 0., 0., 0.};
+#pragma unroll
+  for (int k = 0; k < 6; k++) {
+    const double* const p = mg_part(w, lc, k);
+    for (int q = tid; q < cnt; q += MICRO_TPB) sg[k] += p[q];
+  }
+  micro_reduce2(sg[0], sg[1], sred);
+  micro_reduce2(sg[2], sg[3], sred);
+  micro_reduce2(sg[4], sg[5], sred);
+  if (tid == 0) {
+    double* o = out + MICRO_OUT * lc;
+    for (int k = 0; k < 6; k++) o[k] = sg[k];
+    o[6] = (double)w.st[lc].its;
+    o[7] = w.st[lc].rel;
+    o[8] = (double)w.st[lc].conv;
+  }
+}
+
 // One 3x3 block A(node g, node g+d) of the assembled matrix (MatSetValuesLocal(ADD) +
 // MatAssembly + MatZeroRowsColumns(diag = 1), src/assembly.c:106-112, src/bcs.c:341-347):
 // 0 + Ke_e1 + Ke_e2 + ... over the shared elements in ascending element order (the reference's
@@ -6437,6 +6785,43 @@ void launch_micro_rve(Ctx& c, const MicroArgs& m) {
   else
     hipLaunchKernelGGL(k_micro_rve<false>, dim3(6), dim3(MICRO_TPB), 0, c.stream, m, c.micro_out, c.mnl_ufield,
                        (double*)nullptr);
+}
+
+MicroGridWs mg_layout(double* base, int n) {
+  const int64_t ndof = 3 * (int64_t)n * n * n;
+  MicroGridWs w{};
+  w.vec = base;
+  w.ske = w.vec + 6 * 5 * ndof;
+  w.part = w.ske + 2 * 576;
+  w.npart = (int)mg_npart(n);
+  w.st = reinterpret_cast<MicroGridState*>(w.part + 6 * (int64_t)MG_NPART * w.npart);
+  w.ntile = mg_ntile(n);
+  return w;
+}
+
+void launch_mg_setup(Ctx& c, const MicroArgs& m, const MicroGridWs& w) {
+  const int nn = m.n * m.n * m.n, nt = w.ntile * w.ntile * w.ntile;
+  hipLaunchKernelGGL(k_mg_ke, dim3(1), dim3(MICRO_TPB), 0, c.stream, m, w);
+  hipLaunchKernelGGL(k_mg_init, dim3((nn + MICRO_TPB - 1) / MICRO_TPB, 6), dim3(MICRO_TPB), 0, c.stream, m, w);
+  hipLaunchKernelGGL(k_mg_apply<true>, dim3(nt, 6), dim3(MICRO_TPB), 0, c.stream, m, w);
+  hipLaunchKernelGGL(k_mg_scalar<0>, dim3(6), dim3(MICRO_TPB), 0, c.stream, m, w, nt);
+}
+
+// five launches: q = K p | pq, alpha | x, r, z | its, rel, beta | p
+void launch_mg_iterate(Ctx& c, const MicroArgs& m, const MicroGridWs& w) {
+  const int nt = w.ntile * w.ntile * w.ntile;
+  const int nvb = (int)((3 * (int64_t)m.n * m.n * m.n + MICRO_TPB - 1) / MICRO_TPB);
+  hipLaunchKernelGGL(k_mg_apply<false>, dim3(nt, 6), dim3(MICRO_TPB), 0, c.stream, m, w);
+  hipLaunchKernelGGL(k_mg_scalar<1>, dim3(6), dim3(MICRO_TPB), 0, c.stream, m, w, nt);
+  hipLaunchKernelGGL(k_mg_update, dim3(nvb, 6), dim3(MICRO_TPB), 0, c.stream, m, w);
+  hipLaunchKernelGGL(k_mg_scalar<2>, dim3(6), dim3(MICRO_TPB), 0, c.stream, m, w, nvb);
+  hipLaunchKernelGGL(k_mg_pupdate, dim3(nvb, 6), dim3(MICRO_TPB), 0, c.stream, m, w);
+}
+
+void launch_mg_finish(Ctx& c, const MicroArgs& m, const MicroGridWs& w) {
+  const int nt = w.ntile * w.ntile * w.ntile;
+  hipLaunchKernelGGL(k_mg_stress, dim3(nt, 6), dim3(MICRO_TPB), 0, c.stream, m, w);
+  hipLaunchKernelGGL(k_mg_out, dim3(6), dim3(MICRO_TPB), 0, c.stream, w, nt, c.micro_out);
 }
 
 void launch_mnl_conc(Ctx& c, const MicroNlArgs& a) {

@@ -59,6 +59,8 @@ struct Material {
 constexpr int MICRO_NMAX = 10;      // nodes per edge (micro_n) with the cell solvers' vectors in LDS (micro_mem 0)
 constexpr int MICRO_NMAX_DEV = 20;  // ... with the vectors in device memory (micro_mem 1): one workgroup
                                     // per cell still, and the phase bytes (19^3) stay in LDS
+constexpr int MICRO_NMAX_GRID = 128;  // ... with the grid-wide solver (option micro_solver 1): one
+                                      // workgroup per 8x8x8-node tile of a load case, -mat_law micro only
 constexpr int MICRO_DOFS = 3 * MICRO_NMAX * MICRO_NMAX * MICRO_NMAX;  // LDS vectors are sized for it
 constexpr int MICRO_TPB = 512;
 constexpr int MICRO_OUT = 16;  // doubles a load case leaves: 6 average stresses, iterations, relative norm, converged
@@ -76,6 +78,34 @@ __host__ __device__ inline int micro_phase(int type, int ne, int i, int j, int k
     return a * a + b * b + c * c < ne * ne;
   }
   return 2 * j + 1 < ne;
+}
+
+// option micro_solver 1: the six unit-strain solves spread over the device, one
+// workgroup per tile of MG_T^3 nodes of a load case and one kernel launch per CG phase.  One
+// allocation holds, in this order: the six load cases' five vectors ([6][5][3 n^3]: x, r, p, q,
+// D^-1), the two element matrices, the partial sums ([6][MG_NPART][npart]) and the six state records.
+constexpr int MG_T = 8;       // nodes per tile edge: MG_T^3 = MICRO_TPB threads, one per node
+constexpr int MG_H = MG_T + 2;  // ... of the tile's halo of p in LDS
+constexpr int MG_NPART = 6;   // partial sums a workgroup leaves at most (the stress average's six)
+struct MicroGridState {       // one per load case, written by the scalar kernels only
+  double rz, pq, alpha, beta, norm0, rel;
+  int its, conv, done, pad;
+};
+struct MicroGridWs {
+  double* vec;           // [6][5][ndof]
+  double* ske;           // [2][24][24]
+  double* part;          // [6][MG_NPART][npart]
+  MicroGridState* st;    // [6]
+  int ntile, npart;      // tiles per axis; max(tiles, vector blocks) = the partial arrays' length
+};
+inline int mg_ntile(int n) { return (n + MG_T - 1) / MG_T; }
+inline int64_t mg_npart(int n) {
+  const int64_t t = mg_ntile(n), nt = t * t * t, nvb = (3 * (int64_t)n * n * n + MICRO_TPB - 1) / MICRO_TPB;
+  return nt > nvb ? nt : nvb;
+}
+inline int64_t mg_ws_bytes(int n) {
+  const int64_t ndof = 3 * (int64_t)n * n * n;
+  return (int64_t)sizeof(double) * (6 * 5 * ndof + 2 * 576 + 6 * MG_NPART * mg_npart(n)) + 6 * (int64_t)sizeof(MicroGridState);
 }
 
 // -mat_law micro_nl: the same cell with J2-plastic phases, solved per macro Gauss point.
@@ -393,6 +423,12 @@ struct Ctx {
   int64_t micro_ws_bytes = 0, mnl_ws_bytes = 0;
   int mnl_ws_blocks = 0;       // min(2 x compute units, local Gauss points)
   int mnl_ws_blocks_opt = 0;   // option micro_mem_blocks (testing the walk): > 0 replaces 2 x compute units
+  // option micro_solver: 0 k_micro_rve (one workgroup per load case, micro_mem decides
+  // where its vectors live), 1 the grid-wide solver (-mat_law micro only, micro_n <= MICRO_NMAX_GRID);
+  // micro_grid_poll = CG iterations enqueued between two host polls of the six done flags
+  int micro_solver = 0, micro_grid_poll = 16;
+  double* micro_grid_ws = nullptr;  // mg_ws_bytes(n), allocated at the solver's first use
+  int64_t micro_grid_bytes = 0;
 
   // -mat_law micro_nl: phase Sy / Ka and the Newton settings; the unit-strain fields' strain
   // concentration tensors (with C_hom, after ensure_micro); the slot of every local Gauss point
@@ -475,6 +511,11 @@ void launch_element_ke(Ctx& c);        // Ke of a per-GP-tangent law
 int launch_plain_ke(Ctx& c);           // plain elements, kref, the other elements' Ke (exception-node build)
 void launch_elastic_ke(Ctx& c);        // the elastic law's one element matrix (ke_uni); -mat_law micro: from C_hom
 void launch_micro_rve(Ctx& c, const MicroArgs& m);  // the six unit-strain solves of the micro cell -> micro_out
+// option micro_solver 1: the same six solves, grid-wide
+MicroGridWs mg_layout(double* base, int n);
+void launch_mg_setup(Ctx& c, const MicroArgs& m, const MicroGridWs& w);   // Ke, x, D^-1, r0, p0, the first norm
+void launch_mg_iterate(Ctx& c, const MicroArgs& m, const MicroGridWs& w);  // one gated CG iteration
+void launch_mg_finish(Ctx& c, const MicroArgs& m, const MicroGridWs& w);  // average stresses, state -> micro_out
 // -mat_law micro_nl
 void launch_mnl_conc(Ctx& c, const MicroNlArgs& a);    // mnl_ufield -> mnl_conc
 void launch_mnl_linear(Ctx& c, const MicroNlArgs& a);  // linear test, sigma = C_hom eps, compaction -> mnl_cnt

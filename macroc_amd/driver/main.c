@@ -142,8 +142,11 @@ static int run(int argc, char** argv) {
   /* the flags without an mcx_opts field (-micro_mem, -micro_rtol, -micro_nl_slots, ...) */
   CHK(mcx_apply_args(ctx, argc - 1, (const char* const*)argv + 1));
   const char* micro_mem = "lds";
-  for (int a = 1; a + 1 < argc; a++)
+  int micro_grid = 0; /* -micro_solver grid */
+  for (int a = 1; a + 1 < argc; a++) {
     if (!strcmp(argv[a], "-micro_mem")) micro_mem = argv[a + 1];
+    if (!strcmp(argv[a], "-micro_solver")) micro_grid = !strcmp(argv[a + 1], "grid");
+  }
   mcx_info in;
   CHK(mcx_get_info(ctx, &in));
 #ifdef MCX_WITH_MICROPP
@@ -187,8 +190,8 @@ static int run(int argc, char** argv) {
       PRINTF("id 0 : E = %e\tnu = %e\n", o.micro_mat_1[0], o.micro_mat_1[1]);
       PRINTF("id 1 : E = %e\tnu = %e\n", o.micro_mat_2[0], o.micro_mat_2[1]);
     }
-    PRINTF("Micro cell : type = %d (%s)\tn = %d\tmem = %s\n", o.micro_type, o.micro_type == 0 ? "sphere" : "layer",
-           o.micro_n, micro_mem);
+    PRINTF("Micro cell : type = %d (%s)\tn = %d\tmem = %s%s\n", o.micro_type, o.micro_type == 0 ? "sphere" : "layer",
+           o.micro_n, micro_mem, micro_grid ? "\tsolver = grid" : "");
     PRINTF("C_hom : \n");
     for (int k = 0; k < 6; k++)
       PRINTF("%e\t%e\t%e\t%e\t%e\t%e\n", chom[k * 6], chom[k * 6 + 1], chom[k * 6 + 2], chom[k * 6 + 3],

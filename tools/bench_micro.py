@@ -2,6 +2,10 @@
 -mat_law micro, and mcx_homogenize of -mat_law micro_nl with every Gauss point yielding.
 
     python tools/bench_micro.py --n 10 12 16 20 --mem 1 --points 8 4096
+    python tools/bench_micro.py --n 10 12 16 20 32 64 128 --solver 1 --points
+
+--solver 1 times the grid-wide solver (option micro_solver; -mat_law micro only, so
+give --points nothing); its rows add the launches per CG iteration and --poll sets micro_grid_poll.
 
 Host clock between two mcx_synchronize; the second call of each is reported (the first one
 allocates).  One JSON line per measurement.  --mem -1 leaves the option alone (a library without
@@ -49,6 +53,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, nargs="+", default=[10])
     ap.add_argument("--mem", type=int, default=1, help="option micro_mem (-1: leave it alone)")
+    ap.add_argument("--solver", type=int, default=0, help="option micro_solver: 0 one workgroup per load case, 1 grid-wide")
+    ap.add_argument("--poll", type=int, default=0, help="option micro_grid_poll (0: leave it alone)")
     ap.add_argument("--points", type=int, nargs="*", default=[8, 4096], help="Gauss points of the micro_nl runs")
     ap.add_argument("--root", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     ap.add_argument("--tag", default="")
@@ -60,13 +66,21 @@ def main():
         with M.Macroc(argv_of("micro", n, (2, 2, 2))) as m:
             if a.mem >= 0:
                 m.set_option("micro_mem", a.mem)
+            if a.solver:
+                m.set_option("micro_solver", a.solver)
+                if a.poll:
+                    m.set_option("micro_grid_poll", a.poll)
             m.micro_ctan()
             m.set_option("micro_rtol", 1e-12)  # the default again: marks the cell dirty
             dt = timed(m, m.micro_ctan)
             its = m.micro_ctan()[1]
-        print(json.dumps(dict(tag=a.tag, what="rve", n=n, mem=a.mem, ms=dt * 1e3, cg_its=max(its),
-                              us_per_cg_it=dt * 1e6 / max(max(its), 1))), flush=True)
-        for pts in a.points:
+            dev = m.get_info()["device_bytes"]
+        row = dict(tag=a.tag, what="rve", n=n, mem=a.mem, solver=a.solver, ms=dt * 1e3, cg_its=max(its),
+                   us_per_cg_it=dt * 1e6 / max(max(its), 1))
+        if a.solver:  # five launches per iteration
+            row.update(launches_per_cg_it=5, device_gb=dev / 1e9)
+        print(json.dumps(row), flush=True)
+        for pts in ([] if a.solver else a.points):
             e = round((pts / 8) ** (1.0 / 3.0))
             grid = (e + 1,) * 3
             with M.Macroc(argv_of("micro_nl", n, grid)) as m:
