@@ -416,9 +416,32 @@ int mcx_set_option(void* ctx, const char* name, double value);
 /* the command-line flags that have no mcx_opts field, applied to a context through mcx_set_option:
    -micro_mem lds|device ("micro_mem" 0 | 1), -micro_solver cell|grid ("micro_solver" 0 | 1),
    -micro_rtol, -micro_max_it, -micro_nl_rtol, -micro_nl_max_it, -micro_nl_slots (each with a
-   number).  mcx_parse_args accepts these flags and checks -micro_mem's and -micro_solver's word; call this after mcx_init with the same argv.  Other flags are skipped. */
+   number), -pc_type jacobi|mg ("pc_type" 0 | 1), -pc_mg_levels N, -mg_levels_ksp_max_it k
+   ("pc_mg_smooth").  mcx_parse_args accepts these flags and checks -micro_mem's and -micro_solver's word; call this after mcx_init with the same argv.  Other flags are skipped. */
 int mcx_apply_args(void* ctx, int argc, const char* const* argv);
 int mcx_time_spmv(void* ctx, int iters, double* avg_ms);
+
+/* The macro CG's preconditioner (options of a context; one rank only):
+ * "pc_type" (-pc_type jacobi|mg) 0 (default) Jacobi, 1 a geometric multigrid V-cycle;
+ * "pc_mg_levels" (-pc_mg_levels N) 0 automatic (coarsen until every axis has <= 5 nodes), else
+ * 2 .. 16 levels, refused when the coarsest level would have more than 3072 dofs;
+ * "pc_mg_smooth" (-mg_levels_ksp_max_it k) the Chebyshev degree of the pre- and the post-smoother,
+ * 1 .. 8, default 2.  An axis of N > 2 nodes keeps its even nodes and, when N - 1 is odd, its last
+ * node; the other nodes interpolate 1/2, 1/2; rows of the interpolation at Dirichlet dofs are zero,
+ * the coarse operators are the Galerkin products P^T A P (27 stencil blocks per node), the
+ * coarsest one is inverted densely.  The hierarchy is rebuilt, at the next solve, after every
+ * assembly of the matrix.  With pc_type 1 the solve is PCG with the norm sqrt(r . M^-1 r), the same
+ * reasons, tolerances and history as with Jacobi.  pc_type 0 frees the hierarchy. */
+/* z = M^-1 r on the owned rows with the current preconditioner */
+int mcx_pc_apply(void* ctx, const double* r_host, double* z_host);
+/* the hierarchy of pc_type 1 (nlevels 0 otherwise): node counts nxyz[16][3] from the fine level
+   down, the estimates lmax[16] of the largest eigenvalue of D^-1 A per smoothed level (0 before a
+   matrix is assembled, and for the coarsest level), the hierarchy's device bytes */
+int mcx_pc_mg_info(void* ctx, int* nlevels, int64_t* nxyz, double* lmax, int64_t* bytes);
+/* the operator of level >= 1 in the conventions of the fine level's CSR dump, coarse nodes in
+   natural order (i + j*nx + k*nx*ny)*3+d, every in-grid stencil entry present: rowptr has
+   3*nodes + 1 entries; with colidx and vals NULL only rowptr (and so the entry count) is written */
+int mcx_pc_mg_dump_csr(void* ctx, int level, int64_t* rowptr, int64_t* colidx, double* vals);
 
 #ifdef __cplusplus
 }

@@ -42,6 +42,7 @@ EXPORTS = [
     "mcx_set_micropp", "mcx_set_device_law", "mcx_set_gp_stress", "mcx_set_gp_ctan", "mcx_get_gp_strain",
     "mcx_micro_get_ctan", "mcx_micro_get_phase",
     "mcx_get_gp_ctan", "mcx_micro_nl_get_info", "mcx_micro_nl_get_pool", "mcx_apply_args",
+    "mcx_pc_apply", "mcx_pc_mg_info", "mcx_pc_mg_dump_csr",
 ]
 
 LAWS = {"elastic": 0, "plastic": 1, "external": 2, "micro": 3, "micro_nl": 4}
@@ -191,6 +192,9 @@ def lib():
         getattr(L, fn).argtypes = [vp, d]
     L.mcx_micro_get_ctan.argtypes = [vp, d, C.POINTER(C.c_int), d]
     L.mcx_micro_get_phase.argtypes = [vp, C.POINTER(C.c_ubyte), i64]
+    L.mcx_pc_apply.argtypes = [vp, d, d]
+    L.mcx_pc_mg_info.argtypes = [vp, ip, i64, d, i64]
+    L.mcx_pc_mg_dump_csr.argtypes = [vp, C.c_int, i64, i64, d]
     _LIB = L
     return L
 
@@ -535,6 +539,33 @@ class Macroc:
         y = np.zeros(self.n)
         _check(lib().mcx_spmv(self._ctx, _dp(x), _dp(y)), "mcx_spmv")
         return y
+
+    # ---- the macro CG's preconditioner (options pc_type, pc_mg_levels, pc_mg_smooth)
+    def pc_apply(self, r):
+        """z = M^-1 r on the owned rows with the current preconditioner (Jacobi or the V-cycle)."""
+        r = np.ascontiguousarray(r, dtype=np.float64)
+        assert r.shape == (self.n,)
+        z = np.zeros(self.n)
+        _check(lib().mcx_pc_apply(self._ctx, _dp(r), _dp(z)), "mcx_pc_apply")
+        return z
+
+    def pc_mg_info(self):
+        """the multigrid hierarchy: levels, node counts [levels][3] from the fine level down, the
+        eigenvalue estimates of D^-1 A per level, device bytes (levels 0 under pc_type 0)."""
+        nl, nb = C.c_int(0), C.c_int64(0)
+        nxyz, lmax = np.zeros(48, dtype=np.int64), np.zeros(16)
+        _check(lib().mcx_pc_mg_info(self._ctx, C.byref(nl), _ip(nxyz), _dp(lmax), C.byref(nb)), "mcx_pc_mg_info")
+        n = nl.value
+        return {"levels": n, "nxyz": nxyz.reshape(16, 3)[:n].copy(), "lmax": lmax[:n].copy(), "bytes": nb.value}
+
+    def pc_mg_dump_csr(self, level):
+        """(rowptr, colidx, vals) of the Galerkin operator of level >= 1, coarse natural numbering."""
+        nn = int(np.prod(self.pc_mg_info()["nxyz"][level]))
+        rp = np.zeros(3 * nn + 1, dtype=np.int64)
+        _check(lib().mcx_pc_mg_dump_csr(self._ctx, int(level), _ip(rp), None, None), "mcx_pc_mg_dump_csr")
+        ci, v = np.zeros(rp[-1], dtype=np.int64), np.zeros(rp[-1])
+        _check(lib().mcx_pc_mg_dump_csr(self._ctx, int(level), _ip(rp), _ip(ci), _dp(v)), "mcx_pc_mg_dump_csr")
+        return rp, ci, v
 
     def ksp_history(self):
         n = C.c_int64(0)

@@ -106,6 +106,7 @@ static int free_ctx(Ctx* c) {
                   c->halo.d_recv_idx, c->halo.d_sendbuf, c->halo.d_recvbuf, c->halo.d_bnd};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
+  pcmg_free(*c);
   for (void* p : c->pad_bases) (void)hipFree(p);  // u and the p buffers (dalloc_pad)
   if (c->h_cg) (void)hipHostFree(c->h_cg);
   for (void* h : {(void*)c->h_vib_keys, (void*)c->h_vib_map, (void*)c->h_vib_dict})
@@ -386,7 +387,8 @@ using namespace mcx;
 // command-line flags that are options of a context (mcx_set_option names behind a '-'), not
 // mcx_opts fields: mcx_parse_args accepts them, mcx_apply_args applies them after mcx_init
 static const char* const kApplyFlags[] = {"-micro_mem",     "-micro_rtol",      "-micro_max_it",  "-micro_nl_rtol",
-                                          "-micro_nl_max_it", "-micro_nl_slots", "-micro_solver"};
+                                          "-micro_nl_max_it", "-micro_nl_slots", "-micro_solver",
+                                          "-pc_type",       "-pc_mg_levels",    "-mg_levels_ksp_max_it"};
 static bool apply_flag(const char* k) {
   for (const char* f : kApplyFlags)
     if (!std::strcmp(k, f)) return true;
@@ -520,15 +522,23 @@ int mcx_parse_args(mcx_opts* o, int argc, const char* const* argv) try {
         set_error(std::string("-micro_solver: cell or grid, got ") + (v ? v : "(none)"));
         return 2;
       }
-      a++;
-      continue;
-    }
-    if (!std::strcmp(k, "-ksp_type") || !std::strcmp(k, "-pc_type")) {
-      if (v && std::strcmp(v, !std::strcmp(k, "-ksp_type") ? "cg" : "jacobi")) {
-        set_error(std::string("only -ksp_type cg / -pc_type jacobi are implemented, got ") + v);
+      if (!std::strcmp(k, "-pc_type") && v && std::strcmp(v, "jacobi") && std::strcmp(v, "mg")) {
+        set_error(std::string("only -ksp_type cg / -pc_type jacobi / mg are implemented, got ") + v);
         return 2;
       }
       a++;
+      continue;
+    }
+    if (!std::strcmp(k, "-ksp_type")) {
+      if (v && std::strcmp(v, "cg")) {
+        set_error(std::string("only -ksp_type cg / -pc_type jacobi / mg are implemented, got ") + v);
+        return 2;
+      }
+      a++;
+      continue;
+    }
+    if (!std::strcmp(k, "-pc_mg_galerkin")) {  // the coarse operators are Galerkin products, always
+      if (v && v[0] != '-') a++;
       continue;
     }
     std::fprintf(stderr, "WARNING! There are options you set that were not used: %s\n", k);
@@ -1322,6 +1332,7 @@ int mcx_assembly_jac(void* ctx) try {
   CTX(ctx);
   PhaseTimer t(c, PH_JAC);
   int rc;
+  c.mg.built = false;  // -pc_type mg: the hierarchy is rebuilt at the next solve or mcx_pc_apply
   if ((rc = ensure_micro(c))) return rc;
   const bool table = gp_tangent_law(c.mat.law);
   const bool try_vi = c.o.mat_type == MCX_MAT_AIJ && c.aij_vi && !c.vi_declined;
@@ -1392,7 +1403,7 @@ int mcx_solve(void* ctx, int* its, double* rnorm, int* reason) try {
   int rc;
   {
     PhaseTimer t(c, PH_SOLVE);
-    rc = cg_solve(c, &i0, &n0, &r0);
+    rc = c.pc_type == 1 ? pcmg_solve(c, &i0, &n0, &r0) : cg_solve(c, &i0, &n0, &r0);
   }
   if (rc) return rc;
   MCX_HIP(hipGetLastError());
@@ -1870,6 +1881,95 @@ int mcx_spmv(void* ctx, const double* x_host, double* y_host) try {
   return 0;
 } MCX_CATCH
 
+int mcx_pc_apply(void* ctx, const double* r_host, double* z_host) try {
+  MCX_ENTRY();
+  GUARD(ctx);
+  CTX(ctx);
+  if (!c.assembled) {
+    set_error("mcx_pc_apply: no matrix assembled (call mcx_assembly_jac first)");
+    return 5;
+  }
+  const int64_t n3 = 3 * (int64_t)c.g.nown;
+  MCX_HIP(hipMemcpyAsync(c.tmp, r_host, sizeof(double) * n3, hipMemcpyHostToDevice, c.stream));
+  if (c.pc_type == 1) {
+    int rc = pcmg_apply(c, c.tmp);
+    if (rc) return rc;
+    launch_copy_pad_to_owned(c, c.mg.L[0].x, c.tmp);
+  } else {
+    launch_jacobi(c);
+    launch_pcmg_jacobi(c, n3, c.tmp, c.dinv, c.w);
+  }
+  MCX_HIP(hipGetLastError());
+  MCX_HIP(hipMemcpyAsync(z_host, c.pc_type == 1 ? c.tmp : c.w, sizeof(double) * n3, hipMemcpyDeviceToHost, c.stream));
+  MCX_HIP(hipStreamSynchronize(c.stream));
+  return 0;
+} MCX_CATCH
+
+int mcx_pc_mg_info(void* ctx, int* nlevels, int64_t* nxyz, double* lmax, int64_t* bytes) try {
+  MCX_ENTRY();
+  GUARD(ctx);
+  CTX(ctx);
+  if (nlevels) *nlevels = 0;
+  if (bytes) *bytes = 0;
+  if (c.pc_type != 1) return 0;
+  if (c.assembled) {
+    int rc = pcmg_ensure(c);
+    if (rc) return rc;
+  }
+  int n[PCMG_MAXLEV][3], nl = 0;
+  pcmg_dims(c, c.pc_mg_levels, &nl, n);
+  if (nlevels) *nlevels = nl;
+  for (int l = 0; l < PCMG_MAXLEV; l++) {
+    for (int a = 0; a < 3; a++)
+      if (nxyz) nxyz[3 * l + a] = l < nl ? n[l][a] : 0;
+    if (lmax) lmax[l] = l < nl && c.mg.built ? c.mg.L[l].lmax : 0.;
+  }
+  if (bytes) *bytes = c.mg.bytes;
+  return 0;
+} MCX_CATCH
+
+int mcx_pc_mg_dump_csr(void* ctx, int level, int64_t* rowptr, int64_t* colidx, double* vals) try {
+  MCX_ENTRY();
+  GUARD(ctx);
+  CTX(ctx);
+  if (c.pc_type != 1 || !c.assembled) {
+    set_error("mcx_pc_mg_dump_csr: needs pc_type 1 and an assembled matrix");
+    return 5;
+  }
+  int rc = pcmg_ensure(c);
+  if (rc) return rc;
+  if (level < 1 || level >= c.mg.nlev) {
+    set_error("mcx_pc_mg_dump_csr: level 1 .. " + std::to_string(c.mg.nlev - 1));
+    return 2;
+  }
+  const PcmgLevel& v = c.mg.L[level];
+  std::vector<double> blk;
+  if (vals) {
+    blk.resize((size_t)243 * v.nn);
+    MCX_HIP(hipMemcpyAsync(blk.data(), v.A, sizeof(double) * blk.size(), hipMemcpyDeviceToHost, c.stream));
+    MCX_HIP(hipStreamSynchronize(c.stream));
+  }
+  int64_t pos = 0;
+  if (rowptr) rowptr[0] = 0;
+  for (int64_t p = 0; p < v.nn; p++) {
+    const int i = (int)(p % v.n[0]), j = (int)((p / v.n[0]) % v.n[1]), k = (int)(p / ((int64_t)v.n[0] * v.n[1]));
+    for (int r = 0; r < 3; r++) {
+      for (int nb = 0; nb < 27; nb++) {  // ascending neighbour = ascending column
+        const int ii = i + nb % 3 - 1, jj = j + (nb / 3) % 3 - 1, kk = k + nb / 9 - 1;
+        if (ii < 0 || jj < 0 || kk < 0 || ii >= v.n[0] || jj >= v.n[1] || kk >= v.n[2]) continue;
+        const int64_t q = ii + (int64_t)v.n[0] * (jj + (int64_t)v.n[1] * kk);
+        for (int cc = 0; cc < 3; cc++) {
+          if (colidx) colidx[pos] = 3 * q + cc;
+          if (vals) vals[pos] = blk[(size_t)(nb * 9 + r * 3 + cc) * v.nn + p];
+          pos++;
+        }
+      }
+      if (rowptr) rowptr[3 * p + r + 1] = pos;
+    }
+  }
+  return 0;
+} MCX_CATCH
+
 int mcx_get_ksp_history(void* ctx, double* hist, int64_t* n) try {
   MCX_ENTRY();
   GUARD(ctx);
@@ -2008,6 +2108,38 @@ int mcx_set_option(void* ctx, const char* name, double value) try {
     c.micro_solver = (int)value;
     c.micro_dirty = true;  // C_hom is recomputed by the other solver
     if (!c.micro_solver) return micro_resize(c, &c.micro_grid_ws, &c.micro_grid_bytes, 0);
+    return 0;
+  }
+  if (!std::strcmp(name, "pc_type")) {  // the macro CG's preconditioner: 0 Jacobi, 1 geometric multigrid
+    if (value != 0. && value != 1.) {
+      set_error("pc_type: 0 (jacobi) or 1 (mg)");
+      return 2;
+    }
+    if (value == 1.) {
+      if (int rc = pcmg_check(c, c.pc_mg_levels)) return rc;
+    } else {
+      pcmg_free(c);
+    }
+    c.pc_type = (int)value;
+    return 0;
+  }
+  if (!std::strcmp(name, "pc_mg_levels")) {  // 0: automatic (coarsen until every axis has <= 5 nodes)
+    if (value != (double)(int)value || (value != 0. && (value < 2. || value > (double)PCMG_MAXLEV))) {
+      set_error("pc_mg_levels: 0 (automatic) or 2 .. " + std::to_string(PCMG_MAXLEV));
+      return 2;
+    }
+    if (c.nranks == 1 && !c.comm && !c.lg)  // the level sizes are known now: refuse a coarsest level that is too large
+      if (int rc = pcmg_check(c, (int)value)) return rc;
+    if ((int)value != c.pc_mg_levels) pcmg_free(c);
+    c.pc_mg_levels = (int)value;
+    return 0;
+  }
+  if (!std::strcmp(name, "pc_mg_smooth")) {  // Chebyshev degree of the pre- and the post-smoother
+    if (value != (double)(int)value || value < 1. || value > 8.) {
+      set_error("pc_mg_smooth: 1 .. 8");
+      return 2;
+    }
+    c.pc_mg_smooth = (int)value;
     return 0;
   }
   if (!std::strcmp(name, "micro_grid_poll")) {  // tuning / testing: CG iterations enqueued between two host polls
@@ -2418,10 +2550,16 @@ int mcx_apply_args(void* ctx, int argc, const char* const* argv) try {
         return 2;
       }
       value = std::strcmp(v, "grid") ? 0. : 1.;
+    } else if (!std::strcmp(k, "-pc_type")) {
+      if (std::strcmp(v, "jacobi") && std::strcmp(v, "mg")) {
+        set_error(std::string("only -ksp_type cg / -pc_type jacobi / mg are implemented, got ") + v);
+        return 2;
+      }
+      value = std::strcmp(v, "mg") ? 0. : 1.;
     } else {
       value = std::atof(v);
     }
-    if (int rc = mcx_set_option(ctx, k + 1, value)) return rc;
+    if (int rc = mcx_set_option(ctx, !std::strcmp(k, "-mg_levels_ksp_max_it") ? "pc_mg_smooth" : k + 1, value)) return rc;
   }
   return 0;
 } MCX_CATCH

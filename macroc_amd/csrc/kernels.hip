@@ -8252,4 +8252,359 @@ int cg_iteration(Ctx& c, hipEvent_t ev0, hipEvent_t ev1, bool first, bool last) 
   return reduce_and_logic(c, 2, nbg, RED_BETA, true, c.partials2, c.cg);
 }
 
+// ============================================================================ -pc_type mg
+// Geometric multigrid preconditioner (pcmg.cpp).  All of these are streams: one thread
+// per node, consecutive threads on consecutive nodes, every sum in a fixed order.
+__device__ __forceinline__ int64_t pcmg_at(const PcmgLay& l, int i, int j, int k) {
+  return (i + l.off) + (int64_t)(j + l.off) * l.PX + (int64_t)(k + l.off) * l.PXY;
+}
+
+// coarse parents of fine index f on an axis of N nodes (Nc coarse ones): 1 parent (weight 1) or the
+// two neighbours c0, c0 + 1 (weight 1/2 each).  N <= 2: the axis is not coarsened.  The coarse nodes
+// are the even indices and, when N - 1 is odd, the last node.
+__device__ __forceinline__ int pcmg_parents(int f, int N, int Nc, int& c0) {
+  if (N <= 2) {
+    c0 = f;
+    return 1;
+  }
+  if (f == N - 1 && (f & 1)) {
+    c0 = Nc - 1;
+    return 1;
+  }
+  c0 = f >> 1;
+  return (f & 1) ? 2 : 1;
+}
+// fine children of coarse index c: its own node (weight 1) first, then the odd neighbours that are
+// no coarse nodes themselves (weight 1/2)
+__device__ __forceinline__ int pcmg_children(int c, int N, int f[3]) {
+  if (N <= 2) {
+    f[0] = c;
+    return 1;
+  }
+  const int fi = min(2 * c, N - 1);
+  int m = 0;
+  f[m++] = fi;
+  if (fi - 1 >= 0 && ((fi - 1) & 1) && fi - 1 != N - 1) f[m++] = fi - 1;
+  if (fi + 1 < N && ((fi + 1) & 1) && fi + 1 != N - 1) f[m++] = fi + 1;
+  return m;
+}
+
+__global__ void k_pcmg_mask0(Geo g, unsigned char* __restrict__ mask) {
+  const int n = blockIdx.x * TPB + threadIdx.x;
+  if (n >= g.nown) return;
+  int i, j, k;
+  node_ijk(g, n, i, j, k);
+  mask[n] = (unsigned char)dirichlet_mask(g, g.xs + i, g.ys + j, g.zs + k);
+}
+
+__global__ __launch_bounds__(TPB) void k_pcmg_prolong(PcmgXfer t, PcmgLay lx, const double* __restrict__ xc, int probe,
+                                                      const unsigned char* __restrict__ fmask,
+                                                      double* __restrict__ xf, int add) {
+  const int64_t nf = (int64_t)t.fn[0] * t.fn[1] * t.fn[2];
+  const int64_t n = (int64_t)blockIdx.x * TPB + threadIdx.x;
+  if (n >= nf) return;
+  const int nq = (int)n, i = nq % t.fn[0], j = (nq / t.fn[0]) % t.fn[1], k = nq / (t.fn[0] * t.fn[1]);  // 32-bit divisions
+  int ci, cj, ck;
+  const int mi = pcmg_parents(i, t.fn[0], t.cn[0], ci), mj = pcmg_parents(j, t.fn[1], t.cn[1], cj),
+            mk = pcmg_parents(k, t.fn[2], t.cn[2], ck);
+  const double wt = (mi == 2 ? .5 : 1.) * (mj == 2 ? .5 : 1.) * (mk == 2 ? .5 : 1.);
+  const int pa = probe >= 0 ? (probe / 3) % 3 : 0, pb = probe >= 0 ? (probe / 9) % 3 : 0, pc = probe >= 0 ? probe / 27 : 0,
+            pd = probe >= 0 ? probe % 3 : 0;
+  double v[3] = {0., 0., 0.};
+  for (int c = 0; c < mk; c++)
+    for (int b = 0; b < mj; b++)
+      for (int a = 0; a < mi; a++) {
+        const int I = ci + a, J = cj + b, K = ck + c;
+        if (probe >= 0) {
+          if (I % 3 == pa && J % 3 == pb && K % 3 == pc) v[pd] += wt;
+        } else {
+          const int64_t q = 3 * (I + (int64_t)t.cn[0] * (J + (int64_t)t.cn[1] * K));
+#pragma unroll
+          for (int d = 0; d < 3; d++) v[d] += wt * xc[q + d];
+        }
+      }
+  const int m = fmask[n];
+  const int64_t q = 3 * pcmg_at(lx, i, j, k);
+#pragma unroll
+  for (int d = 0; d < 3; d++) {
+    const double vd = (m >> d & 1) ? 0. : v[d];
+    xf[q + d] = add ? xf[q + d] + vd : vd;
+  }
+}
+
+__global__ __launch_bounds__(TPB) void k_pcmg_restrict(PcmgXfer t, const double* __restrict__ b,
+                                                       const double* __restrict__ w,
+                                                       const unsigned char* __restrict__ fmask,
+                                                       double* __restrict__ bc) {
+  const int64_t ncn = (int64_t)t.cn[0] * t.cn[1] * t.cn[2];
+  const int64_t n = (int64_t)blockIdx.x * TPB + threadIdx.x;
+  if (n >= ncn) return;
+  const int nq = (int)n, I = nq % t.cn[0], J = (nq / t.cn[0]) % t.cn[1], K = nq / (t.cn[0] * t.cn[1]);  // 32-bit divisions
+  int fi[3], fj[3], fk[3];
+  const int mi = pcmg_children(I, t.fn[0], fi), mj = pcmg_children(J, t.fn[1], fj), mk = pcmg_children(K, t.fn[2], fk);
+  double acc[3] = {0., 0., 0.};
+  for (int c = 0; c < mk; c++)
+    for (int bb = 0; bb < mj; bb++)
+      for (int a = 0; a < mi; a++) {
+        const double wt = (a ? .5 : 1.) * (bb ? .5 : 1.) * (c ? .5 : 1.);
+        const int64_t f = fi[a] + (int64_t)t.fn[0] * (fj[bb] + (int64_t)t.fn[1] * fk[c]);
+        const int m = fmask[f];
+#pragma unroll
+        for (int d = 0; d < 3; d++) {
+          const double rv = w ? b[3 * f + d] - w[3 * f + d] : b[3 * f + d];
+          if (!(m >> d & 1)) acc[d] += wt * rv;
+        }
+      }
+#pragma unroll
+  for (int d = 0; d < 3; d++) bc[3 * n + d] = acc[d];
+}
+
+// r = b - A x (b null: r = A x) with A the level's 27 stencil blocks, slot-major
+__global__ __launch_bounds__(TPB) void k_pcmg_spmv(int nx, int ny, int nz, const double* __restrict__ A,
+                                                   const double* __restrict__ x, const double* __restrict__ b,
+                                                   double* __restrict__ r) {
+  const int64_t nn = (int64_t)nx * ny * nz;
+  const int64_t n = (int64_t)blockIdx.x * TPB + threadIdx.x;
+  if (n >= nn) return;
+  const int nq = (int)n, i = nq % nx, j = (nq / nx) % ny, k = nq / (nx * ny);  // 32-bit divisions
+  double acc[3] = {0., 0., 0.};
+  for (int nb = 0; nb < 27; nb++) {
+    const int ii = i + nb % 3 - 1, jj = j + (nb / 3) % 3 - 1, kk = k + nb / 9 - 1;
+    if (ii < 0 || jj < 0 || kk < 0 || ii >= nx || jj >= ny || kk >= nz) continue;
+    const int64_t m = 3 * (ii + (int64_t)nx * (jj + (int64_t)ny * kk));
+    const double x0 = x[m], x1 = x[m + 1], x2 = x[m + 2];
+    const double* a = A + (int64_t)(nb * 9) * nn + n;
+#pragma unroll
+    for (int rr = 0; rr < 3; rr++) {
+      acc[rr] = fma(a[(int64_t)(rr * 3) * nn], x0, acc[rr]);
+      acc[rr] = fma(a[(int64_t)(rr * 3 + 1) * nn], x1, acc[rr]);
+      acc[rr] = fma(a[(int64_t)(rr * 3 + 2) * nn], x2, acc[rr]);
+    }
+  }
+#pragma unroll
+  for (int d = 0; d < 3; d++) r[3 * n + d] = b ? b[3 * n + d] - acc[d] : acc[d];
+}
+
+// Galerkin probe: t = P^T A P e with e the indicator of colour (a, b, c) = (I, J, K) mod 3 and
+// component d.  Node J has at most one neighbour of that colour: t[J] is column d of the block
+// toward it.
+__global__ void k_pcmg_scatter(int nx, int ny, int nz, const double* __restrict__ t, double* __restrict__ A,
+                               int colour, int d) {
+  const int64_t nn = (int64_t)nx * ny * nz;
+  const int64_t n = (int64_t)blockIdx.x * TPB + threadIdx.x;
+  if (n >= nn) return;
+  const int nq = (int)n, i = nq % nx, j = (nq / nx) % ny, k = nq / (nx * ny);  // 32-bit divisions
+  int ox = (colour % 3 - i % 3 + 3) % 3, oy = ((colour / 3) % 3 - j % 3 + 3) % 3, oz = (colour / 9 - k % 3 + 3) % 3;
+  if (ox == 2) ox = -1;
+  if (oy == 2) oy = -1;
+  if (oz == 2) oz = -1;
+  if (i + ox < 0 || i + ox >= nx || j + oy < 0 || j + oy >= ny || k + oz < 0 || k + oz >= nz) return;
+  const int nb = (oz + 1) * 9 + (oy + 1) * 3 + (ox + 1);
+#pragma unroll
+  for (int rr = 0; rr < 3; rr++) A[(int64_t)(nb * 9 + rr * 3 + d) * nn + n] = t[3 * n + rr];
+}
+
+// the level's inverse diagonal; a dof whose Galerkin diagonal is exactly 0 (every fine dof it
+// interpolates to is a Dirichlet dof) gets a unit diagonal and its mask bit
+__global__ void k_pcmg_diag(int64_t nn, double* __restrict__ A, double* __restrict__ dinv,
+                            unsigned char* __restrict__ mask) {
+  const int64_t n = (int64_t)blockIdx.x * TPB + threadIdx.x;
+  if (n >= nn) return;
+  int m = 0;
+#pragma unroll
+  for (int d = 0; d < 3; d++) {
+    double* p = A + (int64_t)(13 * 9 + d * 4) * nn + n;
+    double a = *p;
+    if (a == 0.) {
+      *p = a = 1.;
+      m |= 1 << d;
+    }
+    dinv[3 * n + d] = 1. / a;
+  }
+  mask[n] = (unsigned char)m;
+}
+
+// one Chebyshev step: r = b - w (w null: r = b), d = ca d + cb D^-1 r (dfirst: the first term is
+// dropped), x += d (xzero: x = d)
+__global__ void k_pcmg_cheb(PcmgLay lx, int64_t nn, const double* __restrict__ b, const double* __restrict__ w,
+                            const double* __restrict__ dinv, double* __restrict__ dv, double* __restrict__ x, double ca,
+                            double cb, int dfirst, int xzero) {
+  const int64_t n = (int64_t)blockIdx.x * TPB + threadIdx.x;
+  if (n >= nn) return;
+  const int nq = (int)n, i = nq % lx.nx, j = (nq / lx.nx) % lx.ny, k = nq / (lx.nx * lx.ny);  // 32-bit divisions
+  const int64_t xq = 3 * pcmg_at(lx, i, j, k);
+#pragma unroll
+  for (int d = 0; d < 3; d++) {
+    const int64_t q = 3 * n + d;
+    const double rv = w ? b[q] - w[q] : b[q];
+    const double z = cb * (dinv[q] * rv);
+    const double dn = dfirst ? z : ca * dv[q] + z;
+    dv[q] = dn;
+    x[xq + d] = xzero ? dn : x[xq + d] + dn;
+  }
+}
+
+// x = Ainv b, one wave per row
+__global__ __launch_bounds__(TPB) void k_pcmg_gemv(int n, const double* __restrict__ ainv, const double* __restrict__ b,
+                                                   double* __restrict__ x) {
+  const int row = blockIdx.x * (TPB / 64) + (threadIdx.x >> 6), l = threadIdx.x & 63;
+  if (row >= n) return;
+  const double* a = ainv + (int64_t)row * n;
+  double s = 0.;
+  for (int q = l; q < n; q += 64) s = fma(a[q], b[q], s);
+  s = wave_sum(s);
+  if (l == 0) x[row] = s;
+}
+
+// the power iteration's start vector: the same pseudo-random values in (-1/2, 1/2) every time
+__global__ void k_pcmg_seed(PcmgLay lx, int64_t nn, double* __restrict__ x) {
+  const int64_t n = (int64_t)blockIdx.x * TPB + threadIdx.x;
+  if (n >= nn) return;
+  const int nq = (int)n, i = nq % lx.nx, j = (nq / lx.nx) % lx.ny, k = nq / (lx.nx * lx.ny);  // 32-bit divisions
+  const int64_t xq = 3 * pcmg_at(lx, i, j, k);
+#pragma unroll
+  for (int d = 0; d < 3; d++) {
+    unsigned h = (unsigned)(3 * n + d) * 2654435761u;
+    h ^= h >> 15;
+    h *= 2246822519u;
+    h ^= h >> 13;
+    x[xq + d] = (double)(h & 0xffffffu) * (1. / 16777216.) - .5 + 1. / 33554432.;
+  }
+}
+
+// y = dinv w and the partial sums of y.y
+__global__ __launch_bounds__(TPB) void k_pcmg_scale_dot(int64_t nn, const double* __restrict__ dinv,
+                                                        const double* __restrict__ w, double* __restrict__ y,
+                                                        double* __restrict__ part) {
+  __shared__ double sh[TPB / 64];
+  const int64_t n = (int64_t)blockIdx.x * TPB + threadIdx.x;
+  double s = 0.;
+  if (n < nn) {
+#pragma unroll
+    for (int d = 0; d < 3; d++) {
+      const double v = dinv[3 * n + d] * w[3 * n + d];
+      y[3 * n + d] = v;
+      s += v * v;
+    }
+  }
+  s = block_sum<TPB>(s, sh);
+  if (threadIdx.x == 0) part[blockIdx.x] = s;
+}
+
+__global__ void k_pcmg_scaleto(PcmgLay lx, int64_t nn, const double* __restrict__ y, double s, double* __restrict__ x) {
+  const int64_t n = (int64_t)blockIdx.x * TPB + threadIdx.x;
+  if (n >= nn) return;
+  const int nq = (int)n, i = nq % lx.nx, j = (nq / lx.nx) % lx.ny, k = nq / (lx.nx * lx.ny);  // 32-bit divisions
+  const int64_t xq = 3 * pcmg_at(lx, i, j, k);
+#pragma unroll
+  for (int d = 0; d < 3; d++) x[xq + d] = s * y[3 * n + d];
+}
+
+// partial sums of a . b with a in layout la and b in owned order
+__global__ __launch_bounds__(TPB) void k_pcmg_dot(PcmgLay la, int64_t nn, const double* __restrict__ a,
+                                                  const double* __restrict__ b, double* __restrict__ part) {
+  __shared__ double sh[TPB / 64];
+  const int64_t n = (int64_t)blockIdx.x * TPB + threadIdx.x;
+  double s = 0.;
+  if (n < nn) {
+    const int nq = (int)n, i = nq % la.nx, j = (nq / la.nx) % la.ny, k = nq / (la.nx * la.ny);  // 32-bit divisions
+    const int64_t aq = 3 * pcmg_at(la, i, j, k);
+#pragma unroll
+    for (int d = 0; d < 3; d++) s += a[aq + d] * b[3 * n + d];
+  }
+  s = block_sum<TPB>(s, sh);
+  if (threadIdx.x == 0) part[blockIdx.x] = s;
+}
+
+// p = z + bc p over a whole padded vector (the ghost layer stays 0)
+__global__ void k_pcmg_aypx(int64_t n, const double* __restrict__ z, double bc, double* __restrict__ p, int first) {
+  const int64_t q = (int64_t)blockIdx.x * TPB + threadIdx.x;
+  if (q >= n) return;
+  p[q] = first ? z[q] : z[q] + bc * p[q];
+}
+
+// x += a p, r -= a w (p in layout lp)
+__global__ void k_pcmg_xr(PcmgLay lp, int64_t nn, double a, const double* __restrict__ p, const double* __restrict__ w,
+                          double* __restrict__ x, double* __restrict__ r) {
+  const int64_t n = (int64_t)blockIdx.x * TPB + threadIdx.x;
+  if (n >= nn) return;
+  const int nq = (int)n, i = nq % lp.nx, j = (nq / lp.nx) % lp.ny, k = nq / (lp.nx * lp.ny);  // 32-bit divisions
+  const int64_t pq = 3 * pcmg_at(lp, i, j, k);
+#pragma unroll
+  for (int d = 0; d < 3; d++) {
+    const int64_t q = 3 * n + d;
+    x[q] = x[q] + a * p[pq + d];
+    r[q] = r[q] - a * w[q];
+  }
+}
+
+__global__ void k_pcmg_jacobi(int64_t n, const double* __restrict__ r, const double* __restrict__ dinv,
+                              double* __restrict__ z) {
+  const int64_t q = (int64_t)blockIdx.x * TPB + threadIdx.x;
+  if (q < n) z[q] = r[q] * dinv[q];
+}
+
+PcmgLay pcmg_lay_nat(const int n[3]) { return PcmgLay{n[0], n[1], n[2], n[0], n[0] * n[1], 0}; }
+PcmgLay pcmg_lay_pad(const Ctx& c) { return PcmgLay{c.g.nx, c.g.ny, c.g.nz, c.g.PX, c.g.PX * c.g.PY, 1}; }
+
+void launch_pcmg_mask0(Ctx& c, unsigned char* mask) {
+  hipLaunchKernelGGL(k_pcmg_mask0, dim3(nblk(c.g.nown)), dim3(TPB), 0, c.stream, c.g, mask);
+}
+void launch_pcmg_prolong(Ctx& c, const PcmgXfer& t, const PcmgLay& lx, const double* xc, int probe,
+                         const unsigned char* fmask, double* xf, bool add) {
+  const int64_t nf = (int64_t)t.fn[0] * t.fn[1] * t.fn[2];
+  hipLaunchKernelGGL(k_pcmg_prolong, dim3(nblk(nf)), dim3(TPB), 0, c.stream, t, lx, xc, probe, fmask, xf, add ? 1 : 0);
+}
+void launch_pcmg_restrict(Ctx& c, const PcmgXfer& t, const double* b, const double* w, const unsigned char* fmask,
+                          double* bc) {
+  const int64_t ncn = (int64_t)t.cn[0] * t.cn[1] * t.cn[2];
+  hipLaunchKernelGGL(k_pcmg_restrict, dim3(nblk(ncn)), dim3(TPB), 0, c.stream, t, b, w, fmask, bc);
+}
+void launch_pcmg_spmv(Ctx& c, const PcmgLevel& l, const double* x, const double* b, double* r) {
+  hipLaunchKernelGGL(k_pcmg_spmv, dim3(nblk(l.nn)), dim3(TPB), 0, c.stream, l.n[0], l.n[1], l.n[2], l.A, x, b, r);
+}
+void launch_pcmg_scatter(Ctx& c, const PcmgLevel& l, const double* t, int colour, int d) {
+  hipLaunchKernelGGL(k_pcmg_scatter, dim3(nblk(l.nn)), dim3(TPB), 0, c.stream, l.n[0], l.n[1], l.n[2], t, l.A, colour, d);
+}
+void launch_pcmg_diag(Ctx& c, const PcmgLevel& l) {
+  hipLaunchKernelGGL(k_pcmg_diag, dim3(nblk(l.nn)), dim3(TPB), 0, c.stream, l.nn, l.A, l.dinv, l.mask);
+}
+void launch_pcmg_cheb(Ctx& c, const PcmgLay& lx, int64_t nn, const double* b, const double* w, const double* dinv,
+                      double* d, double* x, double ca, double cb, bool dfirst, bool xzero) {
+  hipLaunchKernelGGL(k_pcmg_cheb, dim3(nblk(nn)), dim3(TPB), 0, c.stream, lx, nn, b, w, dinv, d, x, ca, cb,
+                     dfirst ? 1 : 0, xzero ? 1 : 0);
+}
+void launch_pcmg_gemv(Ctx& c, int n, const double* ainv, const double* b, double* x) {
+  hipLaunchKernelGGL(k_pcmg_gemv, dim3((n + TPB / 64 - 1) / (TPB / 64)), dim3(TPB), 0, c.stream, n, ainv, b, x);
+}
+void launch_pcmg_seed(Ctx& c, const PcmgLay& lx, int64_t nn, double* x) {
+  hipLaunchKernelGGL(k_pcmg_seed, dim3(nblk(nn)), dim3(TPB), 0, c.stream, lx, nn, x);
+}
+// the partial sums of one value -> c.red[0] (k_reduce's fixed tree)
+static void pcmg_reduce(Ctx& c, int nparts) {
+  hipLaunchKernelGGL(k_reduce, dim3(1), dim3(1024), 0, c.stream, c.partials, nparts, 1, c.red, (int)RED_STORE, c.cg,
+                     c.hist, 0, c.cg);
+}
+void launch_pcmg_scale_dot(Ctx& c, int64_t nn, const double* dinv, const double* w, double* y) {
+  hipLaunchKernelGGL(k_pcmg_scale_dot, dim3(nblk(nn)), dim3(TPB), 0, c.stream, nn, dinv, w, y, c.partials);
+  pcmg_reduce(c, (int)nblk(nn));
+}
+void launch_pcmg_scaleto(Ctx& c, const PcmgLay& lx, int64_t nn, const double* y, double s, double* x) {
+  hipLaunchKernelGGL(k_pcmg_scaleto, dim3(nblk(nn)), dim3(TPB), 0, c.stream, lx, nn, y, s, x);
+}
+void launch_pcmg_dot(Ctx& c, const PcmgLay& la, int64_t nn, const double* a, const double* b) {
+  hipLaunchKernelGGL(k_pcmg_dot, dim3(nblk(nn)), dim3(TPB), 0, c.stream, la, nn, a, b, c.partials);
+  pcmg_reduce(c, (int)nblk(nn));
+}
+void launch_pcmg_aypx(Ctx& c, int64_t n, const double* z, double bc, double* p, bool first) {
+  hipLaunchKernelGGL(k_pcmg_aypx, dim3(nblk(n)), dim3(TPB), 0, c.stream, n, z, bc, p, first ? 1 : 0);
+}
+void launch_pcmg_xr(Ctx& c, const PcmgLay& lp, int64_t nn, double a, const double* p, const double* w, double* x,
+                    double* r) {
+  hipLaunchKernelGGL(k_pcmg_xr, dim3(nblk(nn)), dim3(TPB), 0, c.stream, lp, nn, a, p, w, x, r);
+}
+void launch_pcmg_jacobi(Ctx& c, int64_t n, const double* r, const double* dinv, double* z) {
+  hipLaunchKernelGGL(k_pcmg_jacobi, dim3(nblk(n)), dim3(TPB), 0, c.stream, n, r, dinv, z);
+}
+
 }  // namespace mcx

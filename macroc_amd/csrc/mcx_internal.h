@@ -121,6 +121,39 @@ struct MicroNlArgs {
   int nl_max_it;
 };
 
+// -pc_type mg: geometric multigrid preconditioner of the macro CG, one rank.  Level 0
+// is the assembled matrix (launch_spmv, whatever its storage); a coarser level keeps its Galerkin
+// operator as plain stencil blocks, slot-major: value (nb, r, c) of node n at A[(nb*9 + r*3 + c) * nn + n].
+constexpr int PCMG_MAXLEV = 16;
+constexpr int PCMG_COARSE_MAX = 3072;  // dofs of the coarsest level (its inverse is dense)
+// where node (i, j, k) of a vector lives: (i + off) + (j + off) PX + (k + off) PXY.  Owned and coarse
+// vectors: PX = nx, PXY = nx ny, off = 0; the padded box of the fine level (the SpMV's input): off = 1
+struct PcmgLay {
+  int nx, ny, nz, PX, PXY, off;
+};
+struct PcmgXfer {  // node counts of a level and of the next coarser one
+  int fn[3], cn[3];
+};
+struct PcmgLevel {
+  int n[3] = {0, 0, 0};
+  int64_t nn = 0;              // nodes
+  double* A = nullptr;         // [243][nn] (levels >= 1)
+  double* x = nullptr;         // the cycle's iterate (level 0: padded box, shifted by pad_off from x_base)
+  void* x_base = nullptr;
+  double *b = nullptr, *r = nullptr, *d = nullptr, *dinv = nullptr;  // level 0: b = the cycle's argument, r = c.w, d = c.z, dinv = c.dinv
+  unsigned char* mask = nullptr;  // [nn] bit d: dof d is a Dirichlet dof (level >= 1: its Galerkin diagonal was 0)
+  double lmax = 0.;            // estimate of the largest eigenvalue of D^-1 A
+};
+struct Pcmg {
+  int nlev = 0;
+  PcmgLevel L[PCMG_MAXLEV];
+  double* ainv = nullptr;      // dense inverse of the coarsest operator [nc][nc]
+  int nc = 0;                  // its dofs
+  int64_t bytes = 0;           // device memory of the hierarchy (counted in Ctx::device_bytes)
+  bool alloc = false;
+  bool built = false;          // operators, eigenvalue estimates and the inverse belong to the current matrix
+};
+
 struct HaloPlan {
   std::vector<int> nbr_rank;          // neighbour ranks (<= 26)
   std::vector<int64_t> send_off, send_cnt, recv_off, recv_cnt;  // in nodes
@@ -449,6 +482,10 @@ struct Ctx {
   double* mnl_rn = nullptr;      // [ngp] final relative Newton residual
   double* mnl_pool = nullptr;    // [mnl_cap][MNL_WS][8 (n-1)^3]
 
+  // options pc_type (0 Jacobi, 1 multigrid), pc_mg_levels (0: automatic), pc_mg_smooth (Chebyshev degree)
+  int pc_type = 0, pc_mg_levels = 0, pc_mg_smooth = 2;
+  Pcmg mg;
+
   // external Gauss-point law (-mat_law external): host MicroPP-shaped callbacks or a device law
   mcx_micropp_api mpp{};
   bool has_mpp = false;
@@ -554,6 +591,36 @@ int64_t cg_vec_bytes_per_node(const Ctx& c);  // the last solve's CG vector kern
 // z-marching SpMV tile of the current storage (tx, ty, planes per chunk); all 0 for gathered kernels
 void spmv_tile(const Ctx& c, int* tx, int* ty, int* kc);
 int dirichlet_mask_host(const Geo& g, int gi, int gj, int gk);
+
+// ---- -pc_type mg: kernels (kernels.hip) and the hierarchy, cycle and PCG loop (pcmg.cpp)
+void launch_pcmg_mask0(Ctx& c, unsigned char* mask);
+// xf (layout lx) = or += P xc; probe >= 0: xc is the indicator of colour probe / 3, component probe % 3
+void launch_pcmg_prolong(Ctx& c, const PcmgXfer& t, const PcmgLay& lx, const double* xc, int probe,
+                         const unsigned char* fmask, double* xf, bool add);
+void launch_pcmg_restrict(Ctx& c, const PcmgXfer& t, const double* b, const double* w, const unsigned char* fmask,
+                          double* bc);  // bc = P^T (b - w) (w may be null)
+void launch_pcmg_spmv(Ctx& c, const PcmgLevel& l, const double* x, const double* b, double* r);  // r = b - A x (b null: A x)
+void launch_pcmg_scatter(Ctx& c, const PcmgLevel& l, const double* t, int colour, int d);
+void launch_pcmg_diag(Ctx& c, const PcmgLevel& l);
+void launch_pcmg_cheb(Ctx& c, const PcmgLay& lx, int64_t nn, const double* b, const double* w, const double* dinv,
+                      double* d, double* x, double ca, double cb, bool dfirst, bool xzero);
+void launch_pcmg_gemv(Ctx& c, int n, const double* ainv, const double* b, double* x);
+void launch_pcmg_seed(Ctx& c, const PcmgLay& lx, int64_t nn, double* x);
+void launch_pcmg_scale_dot(Ctx& c, int64_t nn, const double* dinv, const double* w, double* y);  // y = dinv w, c.red[0] = y.y
+void launch_pcmg_scaleto(Ctx& c, const PcmgLay& lx, int64_t nn, const double* y, double s, double* x);
+void launch_pcmg_dot(Ctx& c, const PcmgLay& la, int64_t nn, const double* a, const double* b);  // c.red[0] = a.b
+void launch_pcmg_aypx(Ctx& c, int64_t n, const double* z, double bc, double* p, bool first);  // p = z + bc p
+void launch_pcmg_xr(Ctx& c, const PcmgLay& lp, int64_t nn, double a, const double* p, const double* w, double* x,
+                    double* r);  // x += a p, r -= a w
+void launch_pcmg_jacobi(Ctx& c, int64_t n, const double* r, const double* dinv, double* z);  // z = r dinv
+PcmgLay pcmg_lay_nat(const int n[3]);
+PcmgLay pcmg_lay_pad(const Ctx& c);
+int pcmg_dims(const Ctx& c, int levels, int* nlev, int n[][3]);  // the level sizes; levels 0: automatic
+int pcmg_check(Ctx& c, int levels);  // option check: one rank, the coarsest level of `levels` levels fits
+void pcmg_free(Ctx& c);
+int pcmg_ensure(Ctx& c);                                // build or rebuild the hierarchy for the current matrix
+int pcmg_apply(Ctx& c, const double* r_owned);          // mg.L[0].x (padded) = M^-1 r
+int pcmg_solve(Ctx& c, int* its, double* rnorm, int* reason);
 
 }  // namespace mcx
 
