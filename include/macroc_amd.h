@@ -221,6 +221,10 @@ int mcx_local_group_barrier(void* group, int rank);
 int mcx_init_local(const mcx_opts* o, int rank, void* group, void** ctx);
 int mcx_finalize(void* ctx);
 int mcx_get_info(void* ctx, mcx_info* info);
+/* *on = 1 when this context's last SpMV ran the default-stencil march with direct-to-LDS staging
+   (option "vi_st_dma": -1 (default) / 1 where eligible, 0 off; same product bitwise), else 0.  A
+   function of its own: mcx_info keeps its size (ABI revision 3). */
+int mcx_get_st_dma(void* ctx, int* on);
 /* the ranks that actually joined this context's communicator (MPI_Comm_size / MPI_Comm_rank of
    PETSC_COMM_WORLD): ncclCommCount, ncclCommUserRank and ncclCommCuDevice of the RCCL
    communicator; the group size and member rank of the in-process transport; 1, 0 and the

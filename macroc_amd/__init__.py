@@ -42,7 +42,7 @@ EXPORTS = [
     "mcx_set_micropp", "mcx_set_device_law", "mcx_set_gp_stress", "mcx_set_gp_ctan", "mcx_get_gp_strain",
     "mcx_micro_get_ctan", "mcx_micro_get_phase",
     "mcx_get_gp_ctan", "mcx_micro_nl_get_info", "mcx_micro_nl_get_pool", "mcx_apply_args",
-    "mcx_pc_apply", "mcx_pc_mg_info", "mcx_pc_mg_dump_csr",
+    "mcx_pc_apply", "mcx_pc_mg_info", "mcx_pc_mg_dump_csr", "mcx_get_st_dma",
 ]
 
 LAWS = {"elastic": 0, "plastic": 1, "external": 2, "micro": 3, "micro_nl": 4}
@@ -156,6 +156,7 @@ def lib():
     L.mcx_init_local.argtypes = [C.POINTER(Opts), C.c_int, vp, C.POINTER(C.c_void_p)]
     L.mcx_finalize.argtypes = [vp]
     L.mcx_get_info.argtypes = [vp, C.POINTER(Info)]
+    L.mcx_get_st_dma.argtypes = [vp, C.POINTER(C.c_int)]
     L.mcx_comm_info.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.mcx_material_set.argtypes = [vp, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int]
     L.mcx_get_displacement.argtypes = [vp, C.c_int]
@@ -362,10 +363,12 @@ class Macroc:
         _check(lib().mcx_update_vars(self._ctx), "micropp_C_update_vars")
 
     def get_info(self):
-        """mcx_get_info now (storage reflects the last assembly)."""
-        inf = Info()
+        """mcx_get_info now (storage reflects the last assembly), and st_dma: the last SpMV ran the
+        default-stencil march with direct-to-LDS staging (mcx_get_st_dma)."""
+        inf, on = Info(), C.c_int()
         _check(lib().mcx_get_info(self._ctx, C.byref(inf)), "mcx_get_info")
-        return inf.as_dict()
+        _check(lib().mcx_get_st_dma(self._ctx, C.byref(on)), "mcx_get_st_dma")
+        return dict(inf.as_dict(), st_dma=on.value)
 
     def comm_info(self):
         """(ranks in the communicator, this rank in it, HIP device): ncclCommCount /

@@ -673,6 +673,14 @@ int mcx_get_info(void* ctx, mcx_info* in) try {
   return 0;
 } MCX_CATCH
 
+int mcx_get_st_dma(void* ctx, int* on) try {
+  MCX_ENTRY();
+  GUARD(ctx);
+  CTX(ctx);
+  if (on) *on = c.st_dma_last;
+  return 0;
+} MCX_CATCH
+
 int mcx_comm_info(void* ctx, int* comm_ranks, int* comm_rank, int* device) try {
   MCX_ENTRY();
   GUARD(ctx);
@@ -2333,6 +2341,14 @@ int mcx_set_option(void* ctx, const char* name, double value) try {
       set_error("vi_st_l16: partials buffer too small");
       return 2;
     }
+    return 0;
+  }
+  if (!std::strcmp(name, "vi_st_dma")) {  // same grid and partials as k_spmv_st: nothing to re-check
+    if (!(value == -1. || value == 0. || value == 1.)) {
+      set_error("vi_st_dma: -1 (where eligible), 0 or 1");
+      return 1;
+    }
+    c.vi_st_dma = (int)value;
     return 0;
   }
   if (!std::strcmp(name, "vi_st_pf")) {

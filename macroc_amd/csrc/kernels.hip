@@ -17,6 +17,7 @@
 #include <cmath>
 
 #include "mcx_internal.h"
+#include "st_dma_map.h"
 
 namespace mcx {
 
@@ -4874,6 +4875,183 @@ __global__ __launch_bounds__(1024) void k_spmv_st(Geo g, const double* __restric
   }
 }
 
+// k_spmv_st with direct-to-LDS staging (option vi_st_dma, st_dma_map.h).  k_spmv_st loads planes k+3,
+// k+4 into 16 registers per lane and writes them into the 4-slot ring between two barriers, while
+// the VALU and the LDS read path of all 16 waves stand idle.  Here the planes go from memory
+// straight into a 5-slot ring (buffer_load_dwordx4 ... lds, 16 bytes per lane, two per wave and
+// plane): no staging registers, no LDS write pass, and the loads stay in flight across the barriers.
+// Step k (rows read planes k-1 .. k+2):
+//   1. plane k+3 is issued into the slot plane k-2 left (dead since the previous step's last barrier);
+//   2. rows g9 = 0, 1, 2: the only reads of plane k-1 (node k's dz = -1 rows);
+//   3. barrier: every wave is done with plane k-1;
+//   4. plane k+4 is issued into plane k-1's slot;
+//   5. rows g9 = 3 .. 8;
+//   6. s_waitcnt vmcnt(0): this step's two planes (issued at least a third of a step ago) and the
+//      previous step's y stores (issued a whole step ago) have landed;
+//   7. the y stores;
+//   8. barrier: every wave's share of planes k+3, k+4 is in the ring, every wave is done with plane k.
+// `more` and the g9 == 2 branch are block-uniform, so every wave executes the same two barriers per
+// step.  The barriers are raw s_barrier after an explicit lgkmcnt(0) (the rows' ds_reads have
+// returned): __syncthreads() would also drain the loads in flight.  The rows, the masks, the p.w
+// partial and the blocks -> tiles map are k_spmv_st's: y and the partials are bitwise the same.
+// Needs PX even (every staged row and plane then keeps x's alignment mod 16 bytes); sft shifts the
+// staged rows by one double where x is 8 mod 16, so that a lane's 16 source bytes are aligned.
+typedef __attribute__((address_space(3))) void st_lds_void;
+__device__ __forceinline__ void st_dma16(__amdgpu_buffer_rsrc_t r, double* dst, unsigned voff) {
+  __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (st_lds_void*)dst, 16, voff, 0, 0, 0);
+}
+
+template <bool DOT, bool GATED>
+__global__ __launch_bounds__(1024) void k_spmv_st_dma(Geo g, const double* __restrict__ coef,
+                                                      const unsigned long long* __restrict__ mask, int npx, int npy,
+                                                      const double* __restrict__ x, double* __restrict__ y,
+                                                      double* __restrict__ part, const CgState* __restrict__ cg,
+                                                      ZTiling zt, int sft) {
+  constexpr int TX = ST_DMA_TX, TY = ST_DMA_TY, T = TX * TY, RL = ST_DMA_RL, SLOT = ST_DMA_SLOT, NS = ST_DMA_SLOTS;
+  static_assert(RL == vibm_rl<TX, true>() && T == 64 * ST_DMA_WAVES, "k_spmv_st's staged plane");
+  // one LDS array (a second object beside a direct-to-LDS target can cost a vmcnt(0) at every LDS
+  // read): the ring, value 8 of the default stencil's blocks (s9), the reduction scratch (sh)
+  constexpr int S9 = NS * SLOT, SH = S9 + 27, NLDS = SH + T / 64;
+  static_assert(NLDS * sizeof(double) <= 160 * 1024, "the 5-slot ring fits a CU's LDS");
+  __shared__ __attribute__((aligned(16))) double L[NLDS];
+  if (GATED && cg->reason) return;
+  const int b = blockIdx.x;
+  const int xcd = b & 7, t8 = b >> 3;
+  const int slab = (zt.nty + 7) >> 3;
+  const int ty0 = xcd * slab;
+  const int nty_here = min(slab, zt.nty - ty0);
+  const int per = max(nty_here, 0) * zt.ntx * zt.nzc;
+  const int me = threadIdx.x;
+  double dot = 0.;
+  if (t8 >= per) {  // whole block idle (uniform): its (zero) partial
+    if (DOT) {
+      const double s = block_sum<T>(dot, &L[SH]);
+      if (threadIdx.x == 0) part[blockIdx.x] = s;
+    }
+    return;
+  }
+  const int txi = t8 % zt.ntx, r8 = t8 / zt.ntx;
+  const int tyi = ty0 + r8 % nty_here, zc = r8 / nty_here;
+  const int i0 = txi * TX, j0 = tyi * TY;
+  const int k0 = zc * zt.kc, k1 = min(g.nz, k0 + zt.kc);
+  const int wv = __builtin_amdgcn_readfirstlane(me >> 6), ln = me & 63;
+  if (me < 27) L[S9 + me] = coef[me * VIB_STRIDE + 8];
+  const int px = wv & 3, py = wv >> 2;  // 16 x 4 patch of the tile (every wave does the same work)
+  const int lx = px * 16 + (ln & 15), ly = py * 4 + (ln >> 4);
+  const int i = i0 + lx, j = j0 + ly;
+  const bool inxy = i < g.nx && j < g.ny;
+  const int PX = g.PX, PXY = g.PX * g.PY;
+  const int gpx = __builtin_amdgcn_readfirstlane((i0 >> 4) + px), gpy = __builtin_amdgcn_readfirstlane((j0 >> 2) + py);
+  const bool wvin = gpx < npx && gpy < npy;  // (uniform) the patch has a mask
+  const int len = 3 * min(TX + 2, g.nx + 2 - i0);
+  const int rows = min(TY + 2, g.ny + 2 - j0);
+  // the staging map (plane-invariant): this lane's source offsets in its wave's two pieces
+  const int pc0 = st_dma_piece(wv, 0), pc1 = st_dma_piece(wv, 1);
+  const bool has1 = st_dma_piece_ok(pc1);  // (wave-uniform)
+  const unsigned src0 = st_dma_src(pc0, ln, i0, j0, PX, len, rows, sft);
+  const unsigned src1 = has1 ? st_dma_src(pc1, ln, i0, j0, PX, len, rows, sft) : ST_DMA_OOB;
+  // x of padded plane p + 1 (p = -1 .. nz) into the slot at L[so] (zeros outside the box); the record
+  // starts sft doubles ahead of the plane (16-byte aligned: st_dma_map.h)
+  auto dma = [&](int p, int so) {
+    const __amdgpu_buffer_rsrc_t rx = sp_rsrc(x + (int64_t)(p + 1) * PXY * 3 - st_dma_rec_lead(sft) / 8,
+                                              p > g.nz ? 0 : st_dma_rec_bytes(PXY, sft));
+    st_dma16(rx, &L[so + st_dma_dst(pc0)], src0);
+    if (has1) st_dma16(rx, &L[so + st_dma_dst(pc1)], src1);
+  };
+  // prologue: planes k0-1 .. k0+2 in ring slots 0 .. 3
+#pragma unroll
+  for (int s = 0; s < 4; s++) dma(k0 - 1 + s, s * SLOT);
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  typedef const volatile __attribute__((address_space(3))) double lds_vdouble;
+  lds_vdouble* xsv = (lds_vdouble*)&L[0];
+  const int lb = st_dma_read0(lx, ly, sft);  // row dy = -1 of the lane's node within a slot (staged row ly + 1 + dy)
+  int s0 = 0;  // first double of the slot of plane k-1 (a running counter: no modulo in the loops)
+  auto nxt = [&](int so) { return so + SLOT == NS * SLOT ? 0 : so + SLOT; };
+  for (int k = k0; k < k1; k += 2) {
+    const bool two = k + 1 < k1, more = k + 2 < k1;
+    const int s1 = nxt(s0), s2 = nxt(s1), s3 = nxt(s2), s4 = nxt(s3);
+    if (more) dma(k + 3, s4);  // (uniform)
+    unsigned long long m0 = ~0ull, m1 = ~0ull;  // lanes the march leaves (faces, listed rows)
+    if (wvin) {
+      m0 = mask[((int64_t)k * npy + gpy) * npx + gpx];
+      if (two) m1 = mask[((int64_t)(k + 1) * npy + gpy) * npx + gpx];
+    }
+    double ya0 = 0., ya1 = 0., ya2 = 0., yb0 = 0., yb1 = 0., yb2 = 0.;
+    double ca0 = 0., ca1 = 0., ca2 = 0., cb0 = 0., cb1 = 0., cb2 = 0.;
+    int sa = s0, sb = s1, ry = lb;  // the slots of planes k + dz, k + 1 + dz; the lane's row dy in them
+    // the rolled loop over the 9 stencil rows and its scalar-load trick: see k_spmv_st
+#pragma unroll 1
+    for (int g9 = 0; g9 < 9; g9++) {  // stencil row (dy, dz): blocks nb = 3 g9 .. 3 g9 + 2 (dx = -1, 0, 1)
+      double av[27], xa[9], xb[9];
+#pragma unroll
+      for (int t = 0; t < 3; t++) {
+#pragma unroll
+        for (int q = 0; q < 8; q++) av[t * 9 + q] = coef[(g9 * 3 + t) * VIB_STRIDE + q];
+        av[t * 9 + 8] = L[S9 + g9 * 3 + t];
+      }
+      const int ra = sa + ry, rb = sb + ry;
+#pragma unroll
+      for (int q = 0; q < 9; q++) {
+        xa[q] = xsv[ra + q];
+        xb[q] = xsv[rb + q];
+      }
+      __builtin_amdgcn_sched_barrier(0);
+      if (g9 == 4) {  // (uniform) block 13: the node's own x
+        ca0 = xa[3], ca1 = xa[4], ca2 = xa[5];
+        cb0 = xb[3], cb1 = xb[4], cb2 = xb[5];
+      }
+#pragma unroll
+      for (int t = 0; t < 3; t++) {
+#pragma unroll
+        for (int q = 0; q < 9; q++) {
+          const int r = q / 3, cc = q % 3;
+          const double a = av[t * 9 + q];
+          double& ya = r == 0 ? ya0 : (r == 1 ? ya1 : ya2);
+          double& yb = r == 0 ? yb0 : (r == 1 ? yb1 : yb2);
+          ya = __builtin_fma(a, xa[3 * t + cc], ya);
+          yb = __builtin_fma(a, xb[3 * t + cc], yb);
+        }
+      }
+      __builtin_amdgcn_sched_barrier(0);
+      ry += RL;
+      if (g9 == 2 || g9 == 5) {  // (uniform) the next dz
+        ry = lb;
+        sa = sb;
+        sb = nxt(sb);
+      }
+      if (g9 == 2) {  // (uniform) plane k-1 is dead once every wave's rows 0 .. 2 have read it
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+        if (more) dma(k + 4, s0);
+      }
+    }
+    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+    {  // y of both nodes: branch-free buffer stores, a node the march leaves at an out-of-range offset
+      const bool la = inxy && !((m0 >> ln) & 1ull), lb2 = two && inxy && !((m1 >> ln) & 1ull);
+      const int64_t pls = 3 * (int64_t)g.nx * g.ny;
+      const __amdgpu_buffer_rsrc_t ra = sp_rsrc(y + pls * k, pls * 8), rb = sp_rsrc(y + pls * min(k + 1, g.nz - 1), pls * 8);
+      const unsigned o = 24u * (unsigned)(i + g.nx * j), oa = la ? o : SP_OOB, ob = lb2 ? o : SP_OOB;
+      typedef unsigned u32x2v __attribute__((ext_vector_type(2)));
+      __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2v, ya0), ra, oa, 0, 2);
+      __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2v, ya1), ra, oa + 8, 0, 2);
+      __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2v, ya2), ra, oa + 16, 0, 2);
+      __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2v, yb0), rb, ob, 0, 2);
+      __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2v, yb1), rb, ob + 8, 0, 2);
+      __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2v, yb2), rb, ob + 16, 0, 2);
+      if (DOT && la) dot += ca0 * ya0 + ca1 * ya1 + ca2 * ya2;
+      if (DOT && lb2) dot += cb0 * yb0 + cb1 * yb1 + cb2 * yb2;
+    }
+    __builtin_amdgcn_s_barrier();
+    s0 = s2;
+    (void)s3;
+  }
+  if (DOT) {
+    const double s = block_sum<T>(dot, &L[SH]);
+    if (threadIdx.x == 0) part[blockIdx.x] = s;
+  }
+}
+
 // the face phase and the listed rows as a kernel of their own (vi_st_tail 0): SFP_T listed rows per
 // block (the dictionary staged in the patch's LDS), then one face patch per block
 template <bool DOT, bool GATED, bool L16 = true>
@@ -6700,6 +6878,19 @@ static ZTiling sp_tiling(const Ctx& c) {
   return t;
 }
 
+// the march as k_spmv_st_dma (option vi_st_dma: -1 / 1 where eligible, 0 off): k_spmv_st's default form
+// only (no x-pair lanes, no tail, prefetch distance 1), the padded row pitch even, and x one of the
+// padded vectors: pad_off bytes (a multiple of 8) into a 16-byte-aligned allocation with 256 spare
+// bytes, so that every lane's 16 source bytes are aligned once the staged rows are shifted by
+// st_dma_sft doubles, and the shifted record's extra 8 bytes on either side are allocated.  Decided
+// per launch and per rank: both kernels give bitwise the same rows and partials
+static int st_dma_sft(const Ctx& c) { return (c.pad_off / 8) & 1; }
+static bool st_dma_ok(const Ctx& c, const double* xpad) {
+  return c.vi_st_dma != 0 && st_used(c) && !c.vi_st_pair && !c.vi_st_tail && c.vi_st_pf == 1 && c.g.PX % 2 == 0 &&
+         c.pad_off % 8 == 0 && c.pad_off >= 0 && c.pad_off <= 240 &&
+         (reinterpret_cast<uintptr_t>(xpad) - (uintptr_t)c.pad_off) % 16 == 0;
+}
+
 // the listed rows 16 lanes per node (st_tail16) while they fill at most half a resident round of the
 // device (1,024 threads per CU: 8,192 rows on 256 CUs); beyond that one thread per node (st_tail):
 // 16 lanes issue every row's 27 FMAs nine times over, which a long list pays in VALU time.  Measured:
@@ -7636,6 +7827,7 @@ static void sp_dbg(Ctx& c, int nb, const double* xpad, double* y, const ZTiling&
 }
 
 void launch_spmv(Ctx& c, const double* xpad, double* y, bool dot, bool gated) {
+  c.st_dma_last = 0;
   const int nb = (int)spmv_grid_blocks(c);
   const SpmvTiling tl = spmv_tiling(c.g, c.spmv_subl);
   if (c.fmt == FMT_VI && c.vi_block) {
@@ -7694,6 +7886,9 @@ void launch_spmv(Ctx& c, const double* xpad, double* y, bool dot, bool gated) {
     else if (c.vi_st_pf == 2)                                                                                     \
       hipLaunchKernelGGL((k_spmv_st<DV, GV, false, true>), dim3(nb), dim3(1024), 0, c.stream, c.g, c.st_coef,       \
                          c.st_mask, c.st_npx, c.st_npy, xpad, y, c.partials, c.cg, zt);                           \
+    else if ((c.st_dma_last = st_dma_ok(c, xpad)))                                                                \
+      hipLaunchKernelGGL((k_spmv_st_dma<DV, GV>), dim3(nb), dim3(1024), 0, c.stream, c.g, c.st_coef, c.st_mask,     \
+                         c.st_npx, c.st_npy, xpad, y, c.partials, c.cg, zt, st_dma_sft(c));                       \
     else                                                                                                          \
       hipLaunchKernelGGL((k_spmv_st<DV, GV>), dim3(nb), dim3(1024), 0, c.stream, c.g, c.st_coef, c.st_mask,         \
                          c.st_npx, c.st_npy, xpad, y, c.partials, c.cg, zt);                                      \

@@ -374,6 +374,9 @@ struct Ctx {
   int vi_st_pair = 0;        // the march as k_spmv_sp (x-pair lanes, round 6; option vi_st_pair 1; the fused p update
                              // on this path needs it): 0.2920 vs 0.2757 ms for k_spmv_st + k_spmv_face (r06t)
   int vi_st_tail = 0;        // its faces and listed rows in the march's blocks after the march (option vi_st_tail; 0: k_spmv_face)
+  int vi_st_dma = -1;        // the march as k_spmv_st_dma (direct-to-LDS staging, 5-slot ring; option vi_st_dma): -1 / 1 where
+                             // eligible (kernels.hip st_dma_ok), 0 off; same rows bitwise
+  int st_dma_last = 0;       // the last SpMV launched k_spmv_st_dma (mcx_get_st_dma)
   double* st_coef = nullptr;            // [ST_CLASSES][27][VIB_STRIDE] the stencil classes' blocks
   unsigned* st_ids = nullptr;           // [ST_CLASSES][8] their 7 index words, [7] = class usable
   unsigned* st_slot = nullptr;          // [nown] list position + 1 of a non-default node, 0 = default
