@@ -5,7 +5,7 @@ ARCH ?= gfx950
 CXXFLAGS ?= -O3 -std=c++17 -fPIC -ffp-contract=off --offload-arch=$(ARCH) -Wall -Wno-unused-function
 SRC = macroc_amd/csrc/api.cpp macroc_amd/csrc/dmda.cpp macroc_amd/csrc/comm.cpp macroc_amd/csrc/vtu.cpp \
       macroc_amd/csrc/pcmg.cpp macroc_amd/csrc/kernels.hip
-HDR = macroc_amd/csrc/mcx_internal.h macroc_amd/csrc/st_dma_map.h include/macroc_amd.h
+HDR = macroc_amd/csrc/mcx_internal.h macroc_amd/csrc/st_dma_map.h macroc_amd/csrc/pcmg_plan.h include/macroc_amd.h
 LIB = macroc_amd/libmacroc_amd.so
 OBJ = $(patsubst macroc_amd/csrc/%,build/%.o,$(SRC))
 
@@ -77,4 +77,14 @@ $(ASAN_ORACLE): oracle/main.c oracle/oracle.c oracle/oracle.h
 	gcc -O1 -g -ffp-contract=off -fopenmp -std=gnu11 -fsanitize=address,undefined -fno-sanitize-recover=all \
 	  -fno-omit-frame-pointer -o $@ oracle/main.c oracle/oracle.c -lm
 
-.PHONY: all oracle driver driver-mpi testlaw asan clean
+# The multigrid planner (macroc_amd/csrc/pcmg_plan.h: host-only integers) in a stand-alone program under
+# AddressSanitizer + UBSan (tests/test_pcmg_dist_cpu.py builds and runs it; PCMG_PLAN_CHECK: where to put it)
+PCMG_PLAN_CHECK ?= $(ASAN_DIR)/pcmg_plan_check
+HOSTCXX ?= g++
+pcmg-plan-check: $(PCMG_PLAN_CHECK)
+$(PCMG_PLAN_CHECK): tests/csrc/pcmg_plan_check.cpp macroc_amd/csrc/pcmg_plan.h
+	@mkdir -p $(dir $@)
+	$(HOSTCXX) -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all -fno-omit-frame-pointer \
+	  -Wall -Werror -o $@ $<
+
+.PHONY: all oracle driver driver-mpi testlaw asan pcmg-plan-check clean

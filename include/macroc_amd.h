@@ -421,11 +421,11 @@ int mcx_set_option(void* ctx, const char* name, double value);
    -micro_mem lds|device ("micro_mem" 0 | 1), -micro_solver cell|grid ("micro_solver" 0 | 1),
    -micro_rtol, -micro_max_it, -micro_nl_rtol, -micro_nl_max_it, -micro_nl_slots (each with a
    number), -pc_type jacobi|mg ("pc_type" 0 | 1), -pc_mg_levels N, -mg_levels_ksp_max_it k
-   ("pc_mg_smooth").  mcx_parse_args accepts these flags and checks -micro_mem's and -micro_solver's word; call this after mcx_init with the same argv.  Other flags are skipped. */
+   ("pc_mg_smooth"), -pc_mg_dist 0|1 ("pc_mg_dist"; give it before -pc_type).  mcx_parse_args accepts these flags and checks -micro_mem's and -micro_solver's word; call this after mcx_init with the same argv.  Other flags are skipped. */
 int mcx_apply_args(void* ctx, int argc, const char* const* argv);
 int mcx_time_spmv(void* ctx, int iters, double* avg_ms);
 
-/* The macro CG's preconditioner (options of a context; one rank only):
+/* The macro CG's preconditioner (options of a context; one rank only unless "pc_mg_dist" is 1, below):
  * "pc_type" (-pc_type jacobi|mg) 0 (default) Jacobi, 1 a geometric multigrid V-cycle;
  * "pc_mg_levels" (-pc_mg_levels N) 0 automatic (coarsen until every axis has <= 5 nodes), else
  * 2 .. 16 levels, refused when the coarsest level would have more than 3072 dofs;
@@ -436,16 +436,44 @@ int mcx_time_spmv(void* ctx, int iters, double* avg_ms);
  * coarsest one is inverted densely.  The hierarchy is rebuilt, at the next solve, after every
  * assembly of the matrix.  With pc_type 1 the solve is PCG with the norm sqrt(r . M^-1 r), the same
  * reasons, tolerances and history as with Jacobi.  pc_type 0 frees the hierarchy. */
-/* z = M^-1 r on the owned rows with the current preconditioner */
+/* "pc_mg_dist" (-pc_mg_dist 0|1, default 0; other values fail with code 1): on a context with a
+ * communicator (several ranks, or one rank with a communicator id; either transport) pc_type 1 is
+ * refused with code 2 ("one rank only") unless pc_mg_dist is 1, set first.  With it the hierarchy is
+ * the same operator M^-1 as on one rank, up to the summation order of the dot products, distributed
+ * like the grid: coarse node I of an axis sits on fine node min(2 I, N - 1) and belongs to that node's
+ * owner (the fine ranges are the DMDA's), every level's vectors live in the rank's box plus one ghost
+ * layer, and the coarsest level is gathered by one all-reduce and solved on every rank.  Automatic
+ * levels (pc_mg_levels 0) also stop before a level on which some rank would own no node on some
+ * axis; a fixed pc_mg_levels that reaches such a level is refused with code 2, the message naming
+ * the level, the axis and the rank.  Every rank decides this from the options alone, so all ranks
+ * refuse alike.  Setting pc_mg_dist back to 0 while pc_type is 1 on such a context fails with code 2;
+ * on a context without a communicator the option is accepted and changes nothing.  With it,
+ * mcx_solve, mcx_pc_apply, mcx_pc_mg_info and mcx_pc_mg_dump_csr are collective (every rank calls
+ * them in the same order), and every rank gets the same iteration count, norms and history.
+ * Off by default: the RCCL transport's send/recv has not run between two GPUs yet. */
+/* z = M^-1 r on the owned rows with the current preconditioner (owned rows in, owned rows out) */
 int mcx_pc_apply(void* ctx, const double* r_host, double* z_host);
 /* the hierarchy of pc_type 1 (nlevels 0 otherwise): node counts nxyz[16][3] from the fine level
    down, the estimates lmax[16] of the largest eigenvalue of D^-1 A per smoothed level (0 before a
-   matrix is assembled, and for the coarsest level), the hierarchy's device bytes */
+   matrix is assembled, and for the coarsest level), the hierarchy's device bytes (pc_mg_dist: the
+   global node counts, the same lmax on every rank, this rank's bytes) */
 int mcx_pc_mg_info(void* ctx, int* nlevels, int64_t* nxyz, double* lmax, int64_t* bytes);
 /* the operator of level >= 1 in the conventions of the fine level's CSR dump, coarse nodes in
    natural order (i + j*nx + k*nx*ny)*3+d, every in-grid stencil entry present: rowptr has
-   3*nodes + 1 entries; with colidx and vals NULL only rowptr (and so the entry count) is written */
+   3*nodes + 1 entries; with colidx and vals NULL only rowptr (and so the entry count) is written.
+   pc_mg_dist: the rows are the rank's owned coarse nodes in the natural order of its box (x fastest,
+   mcx_pc_mg_box), colidx is in the level's global natural numbering */
 int mcx_pc_mg_dump_csr(void* ctx, int level, int64_t* rowptr, int64_t* colidx, double* vals);
+/* Host-only (no GPU, no context): the box rank `rank` of the rank grid o->px x o->py x o->pz (all
+   three given, rank = pi + px (pj + py pk)) owns on every level of the distributed hierarchy of the
+   grid o->NX x NY x NZ with pc_mg_levels `levels` (0: automatic): *nlevels, and global start[16][3]
+   and count[16][3] from the fine level down (0 beyond *nlevels; any pointer may be NULL).  Code 1:
+   bad arguments; code 2: what "pc_type" 1 would refuse (a rank without a node, a coarsest level
+   above 3072 dofs, no coarser level). */
+int mcx_pc_mg_plan(const mcx_opts* o, int rank, int levels, int* nlevels, int64_t* start, int64_t* count);
+/* the same for a live context and one level: global start[3] and count[3] of the box this rank owns
+   (the whole level without pc_mg_dist or without a communicator) */
+int mcx_pc_mg_box(void* ctx, int level, int64_t* start, int64_t* count);
 
 #ifdef __cplusplus
 }

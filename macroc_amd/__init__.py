@@ -42,7 +42,7 @@ EXPORTS = [
     "mcx_set_micropp", "mcx_set_device_law", "mcx_set_gp_stress", "mcx_set_gp_ctan", "mcx_get_gp_strain",
     "mcx_micro_get_ctan", "mcx_micro_get_phase",
     "mcx_get_gp_ctan", "mcx_micro_nl_get_info", "mcx_micro_nl_get_pool", "mcx_apply_args",
-    "mcx_pc_apply", "mcx_pc_mg_info", "mcx_pc_mg_dump_csr", "mcx_get_st_dma",
+    "mcx_pc_apply", "mcx_pc_mg_info", "mcx_pc_mg_dump_csr", "mcx_get_st_dma", "mcx_pc_mg_plan", "mcx_pc_mg_box",
 ]
 
 LAWS = {"elastic": 0, "plastic": 1, "external": 2, "micro": 3, "micro_nl": 4}
@@ -196,6 +196,8 @@ def lib():
     L.mcx_pc_apply.argtypes = [vp, d, d]
     L.mcx_pc_mg_info.argtypes = [vp, ip, i64, d, i64]
     L.mcx_pc_mg_dump_csr.argtypes = [vp, C.c_int, i64, i64, d]
+    L.mcx_pc_mg_plan.argtypes = [C.POINTER(Opts), C.c_int, C.c_int, ip, i64, i64]
+    L.mcx_pc_mg_box.argtypes = [vp, C.c_int, i64, i64]
     _LIB = L
     return L
 
@@ -255,6 +257,18 @@ def plan_halo(argv, rank=0, nranks=1):
         so += sc[q]
         ro += rc[q]
     return out
+
+
+def pc_mg_plan(argv, rank=0, levels=0):
+    """Host-only: the boxes rank `rank` of the rank grid -da_processors_x/y/z owns on every level of
+    the distributed multigrid hierarchy (option pc_mg_dist): (start [levels][3], count [levels][3]),
+    global indices from the fine level down.  Raises what pc_type 1 would refuse."""
+    o = parse_args(argv)
+    nl = C.c_int(0)
+    start, count = np.zeros(48, dtype=np.int64), np.zeros(48, dtype=np.int64)
+    _check(lib().mcx_pc_mg_plan(C.byref(o), int(rank), int(levels), C.byref(nl), _ip(start), _ip(count)),
+           "mcx_pc_mg_plan")
+    return start.reshape(16, 3)[: nl.value].copy(), count.reshape(16, 3)[: nl.value].copy()
 
 
 class LocalGroup:
@@ -561,9 +575,19 @@ class Macroc:
         n = nl.value
         return {"levels": n, "nxyz": nxyz.reshape(16, 3)[:n].copy(), "lmax": lmax[:n].copy(), "bytes": nb.value}
 
+    def pc_mg_box(self, level):
+        """(start [3], count [3]): the box of level `level` this rank owns, global indices."""
+        start, count = np.zeros(3, dtype=np.int64), np.zeros(3, dtype=np.int64)
+        _check(lib().mcx_pc_mg_box(self._ctx, int(level), _ip(start), _ip(count)), "mcx_pc_mg_box")
+        return start, count
+
     def pc_mg_dump_csr(self, level):
-        """(rowptr, colidx, vals) of the Galerkin operator of level >= 1, coarse natural numbering."""
-        nn = int(np.prod(self.pc_mg_info()["nxyz"][level]))
+        """(rowptr, colidx, vals) of the Galerkin operator of level >= 1: the rows of this rank's owned
+        coarse nodes (pc_mg_box; one rank: all), columns in the level's global natural numbering."""
+        sizes = self.pc_mg_info()["nxyz"]  # builds the hierarchy (collective under pc_mg_dist)
+        if not 1 <= level < len(sizes):  # the library's refusal
+            _check(lib().mcx_pc_mg_dump_csr(self._ctx, int(level), None, None, None), "mcx_pc_mg_dump_csr")
+        nn = int(np.prod(self.pc_mg_box(level)[1]))
         rp = np.zeros(3 * nn + 1, dtype=np.int64)
         _check(lib().mcx_pc_mg_dump_csr(self._ctx, int(level), _ip(rp), None, None), "mcx_pc_mg_dump_csr")
         ci, v = np.zeros(rp[-1], dtype=np.int64), np.zeros(rp[-1])

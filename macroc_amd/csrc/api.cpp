@@ -193,7 +193,10 @@ static int init_ctx(Ctx& c, const mcx_opts* o, int rank, int nranks, const void*
     for (hipEvent_t& e : pr) MCX_HIP(hipEventCreate(&e));
   for (int q = 0; q < 2; q++) MCX_HIP(hipEventCreateWithFlags(&c.ev_chunk[q], hipEventDisableTiming));
   if ((rc = comm_init(c, comm_id))) return rc;
-  if ((rc = build_halo_plan(c))) return rc;
+  {
+    const int n3[3] = {c.g.nx, c.g.ny, c.g.nz};
+    if ((rc = build_halo_plan(c, c.halo, n3, c.g.PX, c.g.PX * c.g.PY, &c.device_bytes))) return rc;
+  }
   if ((rc = upload_constants(c))) return rc;
   const Geo& g = c.g;
   const int64_t npad = (int64_t)g.PX * g.PY * g.PZ * 3, nown3 = 3 * (int64_t)g.nown, E = g.nelem;
@@ -388,7 +391,8 @@ using namespace mcx;
 // mcx_opts fields: mcx_parse_args accepts them, mcx_apply_args applies them after mcx_init
 static const char* const kApplyFlags[] = {"-micro_mem",     "-micro_rtol",      "-micro_max_it",  "-micro_nl_rtol",
                                           "-micro_nl_max_it", "-micro_nl_slots", "-micro_solver",
-                                          "-pc_type",       "-pc_mg_levels",    "-mg_levels_ksp_max_it"};
+                                          "-pc_type",       "-pc_mg_levels",    "-mg_levels_ksp_max_it",
+                                          "-pc_mg_dist"};
 static bool apply_flag(const char* k) {
   for (const char* f : kApplyFlags)
     if (!std::strcmp(k, f)) return true;
@@ -731,7 +735,8 @@ int mcx_plan_halo(const mcx_opts* o, int rank, int nranks, int* nnbr, int* nbr_r
   int rc = setup_decomposition(c);
   if (rc) return rc;
   std::vector<int> sidx, ridx;
-  plan_halo(c, sidx, ridx);
+  const int n3[3] = {c.g.nx, c.g.ny, c.g.nz};
+  plan_halo(c, c.halo, n3, c.g.PX, c.g.PX * c.g.PY, sidx, ridx);
   const HaloPlan& h = c.halo;
   if (nnbr) *nnbr = (int)h.nbr_rank.size();
   if (nsend) *nsend = h.nsend;
@@ -1950,6 +1955,8 @@ int mcx_pc_mg_dump_csr(void* ctx, int level, int64_t* rowptr, int64_t* colidx, d
     set_error("mcx_pc_mg_dump_csr: level 1 .. " + std::to_string(c.mg.nlev - 1));
     return 2;
   }
+  // rows: the rank's owned coarse nodes in the natural order of its box; columns: the level's global
+  // natural numbering (one rank: the same thing)
   const PcmgLevel& v = c.mg.L[level];
   std::vector<double> blk;
   if (vals) {
@@ -1960,12 +1967,13 @@ int mcx_pc_mg_dump_csr(void* ctx, int level, int64_t* rowptr, int64_t* colidx, d
   int64_t pos = 0;
   if (rowptr) rowptr[0] = 0;
   for (int64_t p = 0; p < v.nn; p++) {
-    const int i = (int)(p % v.n[0]), j = (int)((p / v.n[0]) % v.n[1]), k = (int)(p / ((int64_t)v.n[0] * v.n[1]));
+    const int i = (int)(p % v.n[0]) + v.s[0], j = (int)((p / v.n[0]) % v.n[1]) + v.s[1],
+              k = (int)(p / ((int64_t)v.n[0] * v.n[1])) + v.s[2];
     for (int r = 0; r < 3; r++) {
       for (int nb = 0; nb < 27; nb++) {  // ascending neighbour = ascending column
         const int ii = i + nb % 3 - 1, jj = j + (nb / 3) % 3 - 1, kk = k + nb / 9 - 1;
-        if (ii < 0 || jj < 0 || kk < 0 || ii >= v.n[0] || jj >= v.n[1] || kk >= v.n[2]) continue;
-        const int64_t q = ii + (int64_t)v.n[0] * (jj + (int64_t)v.n[1] * kk);
+        if (ii < 0 || jj < 0 || kk < 0 || ii >= v.N[0] || jj >= v.N[1] || kk >= v.N[2]) continue;
+        const int64_t q = ii + (int64_t)v.N[0] * (jj + (int64_t)v.N[1] * kk);
         for (int cc = 0; cc < 3; cc++) {
           if (colidx) colidx[pos] = 3 * q + cc;
           if (vals) vals[pos] = blk[(size_t)(nb * 9 + r * 3 + cc) * v.nn + p];
@@ -1974,6 +1982,55 @@ int mcx_pc_mg_dump_csr(void* ctx, int level, int64_t* rowptr, int64_t* colidx, d
       }
       if (rowptr) rowptr[3 * p + r + 1] = pos;
     }
+  }
+  return 0;
+} MCX_CATCH
+
+// host-only: the box of rank `rank` of the rank grid o->px x py x pz on every level
+int mcx_pc_mg_plan(const mcx_opts* o, int rank, int levels, int* nlevels, int64_t* start, int64_t* count) try {
+  MCX_ENTRY();
+  if (!o || o->px < 1 || o->py < 1 || o->pz < 1 || levels < 0 || levels == 1 || levels > PCMG_MAXLEV) {
+    set_error("mcx_pc_mg_plan: needs options with the rank grid given (-da_processors_x/y/z >= 1) and levels 0 or 2 .. " +
+              std::to_string(PCMG_MAXLEV));
+    return 1;
+  }
+  if (o->NX < 2 || o->NY < 2 || o->NZ < 2 || o->NX > INT32_MAX || o->NY > INT32_MAX || o->NZ > INT32_MAX) {
+    set_error("mcx_pc_mg_plan: grid needs 2 .. 2^31 - 1 nodes per direction");
+    return 1;
+  }
+  const int N0[3] = {(int)o->NX, (int)o->NY, (int)o->NZ}, mnp[3] = {o->px, o->py, o->pz};
+  if (rank < 0 || rank >= mnp[0] * mnp[1] * mnp[2]) {
+    set_error("mcx_pc_mg_plan: rank outside the rank grid");
+    return 1;
+  }
+  PcmgPlan P;
+  std::string err;
+  if (int rc = pcmg_plan_checked(N0, mnp, rank, levels, &P, &err)) {
+    set_error(err);
+    return rc;
+  }
+  if (nlevels) *nlevels = P.nlev;
+  for (int l = 0; l < PCMG_MAXLEV; l++)
+    for (int a = 0; a < 3; a++) {
+      if (start) start[3 * l + a] = l < P.nlev ? P.s[l][a] : 0;
+      if (count) count[3 * l + a] = l < P.nlev ? P.n[l][a] : 0;
+    }
+  return 0;
+} MCX_CATCH
+
+int mcx_pc_mg_box(void* ctx, int level, int64_t* start, int64_t* count) try {
+  MCX_ENTRY();
+  GUARD(ctx);
+  CTX(ctx);
+  PcmgPlan P;
+  if (int rc = pcmg_plan_ctx(c, c.pc_mg_levels, &P)) return rc;
+  if (level < 0 || level >= P.nlev) {
+    set_error("mcx_pc_mg_box: level 0 .. " + std::to_string(P.nlev - 1));
+    return 2;
+  }
+  for (int a = 0; a < 3; a++) {
+    if (start) start[a] = P.s[level][a];
+    if (count) count[a] = P.n[level][a];
   }
   return 0;
 } MCX_CATCH
@@ -2118,6 +2175,20 @@ int mcx_set_option(void* ctx, const char* name, double value) try {
     if (!c.micro_solver) return micro_resize(c, &c.micro_grid_ws, &c.micro_grid_bytes, 0);
     return 0;
   }
+  if (!std::strcmp(name, "pc_mg_dist")) {  // 1: pc_type 1 on a context with a communicator (the distributed hierarchy)
+    if (value != 0. && value != 1.) {
+      set_error("pc_mg_dist: 0 (pc_type mg on one rank only) or 1 (the hierarchy distributed over the ranks)");
+      return 1;
+    }
+    const bool multi = c.nranks > 1 || c.comm || c.lg;
+    if (value == 0. && c.pc_mg_dist && c.pc_type == 1 && multi) {
+      set_error("pc_mg_dist 0: pc_type is 1 on rank " + std::to_string(c.rank) + " of " + std::to_string(c.nranks) +
+                " (set pc_type 0 first)");
+      return 2;
+    }
+    c.pc_mg_dist = (int)value;  // without a communicator it changes nothing
+    return 0;
+  }
   if (!std::strcmp(name, "pc_type")) {  // the macro CG's preconditioner: 0 Jacobi, 1 geometric multigrid
     if (value != 0. && value != 1.) {
       set_error("pc_type: 0 (jacobi) or 1 (mg)");
@@ -2136,7 +2207,9 @@ int mcx_set_option(void* ctx, const char* name, double value) try {
       set_error("pc_mg_levels: 0 (automatic) or 2 .. " + std::to_string(PCMG_MAXLEV));
       return 2;
     }
-    if (c.nranks == 1 && !c.comm && !c.lg)  // the level sizes are known now: refuse a coarsest level that is too large
+    // the level sizes are known now: refuse a coarsest level that is too large (pc_mg_dist: or a level
+    // that leaves a rank without a node; every rank decides alike, from the options alone)
+    if ((c.nranks == 1 && !c.comm && !c.lg) || c.pc_mg_dist)
       if (int rc = pcmg_check(c, (int)value)) return rc;
     if ((int)value != c.pc_mg_levels) pcmg_free(c);
     c.pc_mg_levels = (int)value;

@@ -79,6 +79,7 @@ static const char* bar_name(int tag) {
     case BAR_RED_IN: return "all-reduce (partials)";
     case BAR_RED_SUM: return "all-reduce (summed)";
     case BAR_FINALIZE: return "mcx_finalize";
+    case BAR_MG_ALLOC: return "multigrid hierarchy (allocated)";
     default: return "mcx_local_group_barrier";
   }
 }
@@ -202,15 +203,19 @@ int comm_wait(Ctx& c, hipEvent_t ev, const char* what) {
 //   halo_finish: the compute stream waits for the exchange and unpacks into the ghost layer.
 // halo_exchange = start + finish.  Anything enqueued on the compute stream in between overlaps
 // the exchange (cg_iteration: the interior p update).
-int halo_start(Ctx& c, double* xpad) {
-  if (c.nranks <= 1 || c.halo.nbr_rank.empty()) return 0;
+// A plan other than the context's own (h.level >= 1: a multigrid level's box, pc_mg_dist) exchanges
+// with the neighbours' plans of the same level; the events and the barrier tags are shared, every
+// exchange being complete on the host side before the next one starts.
+static const HaloPlan& peer_plan(const Ctx& q, const HaloPlan& h) { return h.level < 0 ? q.halo : q.mg.L[h.level].halo; }
+
+int halo_start(Ctx& c, HaloPlan& h, double* xpad) {
+  if (c.nranks <= 1 || h.nbr_rank.empty()) return 0;
   if (int rc = comm_check(c)) return rc;
-  HaloPlan& h = c.halo;
   if (c.lg) {
     LocalGroup* g = c.lg;
     // neighbours finished reading my previous send buffer
     for (int q : h.nbr_rank) MCX_HIP(hipStreamWaitEvent(c.stream, g->ev_halo_done[q], 0));
-    launch_pack(c, xpad);
+    launch_pack(c, h, xpad);
     MCX_HIP(hipEventRecord(g->ev_packed[c.rank], c.stream));
     // the copies below overwrite my receive buffer: order them after my compute stream's last
     // reader of it (the previous halo's k_unpack), as the RCCL branch does
@@ -218,14 +223,15 @@ int halo_start(Ctx& c, double* xpad) {
     if (int rc = group_barrier(g, c.rank, BAR_HALO_PACKED, c.comm_timeout)) return rc;
     for (size_t t = 0; t < h.nbr_rank.size(); t++) {
       const Ctx& q = *g->members[h.nbr_rank[t]];
+      const HaloPlan& qh = peer_plan(q, h);
       size_t idx = 0;
-      while (idx < q.halo.nbr_rank.size() && q.halo.nbr_rank[idx] != c.rank) idx++;
-      if (idx == q.halo.nbr_rank.size() || q.halo.send_cnt[idx] != h.recv_cnt[t]) {
+      while (idx < qh.nbr_rank.size() && qh.nbr_rank[idx] != c.rank) idx++;
+      if (idx == qh.nbr_rank.size() || qh.send_cnt[idx] != h.recv_cnt[t] || !qh.d_sendbuf) {
         set_error("local halo: inconsistent neighbour plans");
         return 22;
       }
       MCX_HIP(hipStreamWaitEvent(c.comm_stream, g->ev_packed[h.nbr_rank[t]], 0));
-      MCX_HIP(hipMemcpyAsync(h.d_recvbuf + 3 * h.recv_off[t], q.halo.d_sendbuf + 3 * q.halo.send_off[idx],
+      MCX_HIP(hipMemcpyAsync(h.d_recvbuf + 3 * h.recv_off[t], qh.d_sendbuf + 3 * qh.send_off[idx],
                              sizeof(double) * 3 * h.recv_cnt[t], hipMemcpyDeviceToDevice, c.comm_stream));
     }
     MCX_HIP(hipEventRecord(g->ev_halo_done[c.rank], c.comm_stream));
@@ -234,7 +240,7 @@ int halo_start(Ctx& c, double* xpad) {
     if (int rc = group_barrier(g, c.rank, BAR_HALO_DONE, c.comm_timeout)) return rc;
     return 0;
   }
-  launch_pack(c, xpad);
+  launch_pack(c, h, xpad);
   MCX_HIP(hipEventRecord(c.ev_pack, c.stream));
   MCX_HIP(hipStreamWaitEvent(c.comm_stream, c.ev_pack, 0));
   MCX_NCCL(ncclGroupStart());
@@ -249,19 +255,20 @@ int halo_start(Ctx& c, double* xpad) {
   return 0;
 }
 
-int halo_finish(Ctx& c, double* xpad) {
-  if (c.nranks <= 1 || c.halo.nbr_rank.empty()) return 0;
+int halo_finish(Ctx& c, HaloPlan& h, double* xpad) {
+  if (c.nranks <= 1 || h.nbr_rank.empty()) return 0;
   MCX_HIP(hipStreamWaitEvent(c.stream, c.ev_comm, 0));
-  launch_unpack(c, xpad);
+  launch_unpack(c, h, xpad);
   return 0;
 }
 
-int halo_exchange(Ctx& c, double* xpad) {
-  int rc = halo_start(c, xpad);
-  return rc ? rc : halo_finish(c, xpad);
+int halo_exchange(Ctx& c, HaloPlan& h, double* xpad) {
+  int rc = halo_start(c, h, xpad);
+  return rc ? rc : halo_finish(c, h, xpad);
 }
 
-static int allreduce_op(Ctx& c, const double* in, double* out, int count, int op) {
+// ptrs: the device table of every member's `in` (in-process transport only)
+static int allreduce_op(Ctx& c, const double* in, double* out, int count, int op, const double* const* ptrs) {
   if (int rc = comm_check(c)) return rc;
   if (c.nranks <= 1 && !c.comm) {
     if (in != out) MCX_HIP(hipMemcpyAsync(out, in, sizeof(double) * count, hipMemcpyDeviceToDevice, c.stream));
@@ -272,7 +279,7 @@ static int allreduce_op(Ctx& c, const double* in, double* out, int count, int op
     MCX_HIP(hipEventRecord(g->ev_red[c.rank], c.stream));
     if (int rc = group_barrier(g, c.rank, BAR_RED_IN, c.comm_timeout)) return rc;
     for (int q = 0; q < g->nranks; q++) MCX_HIP(hipStreamWaitEvent(c.stream, g->ev_red[q], 0));
-    launch_group_sum(c, (const double* const*)g->d_red_ptrs, g->nranks, count, out, op);
+    launch_group_sum(c, ptrs, g->nranks, count, out, op);
     MCX_HIP(hipEventRecord(g->ev_sum[c.rank], c.stream));
     if (int rc = group_barrier(g, c.rank, BAR_RED_SUM, c.comm_timeout)) return rc;
     return 0;
@@ -282,8 +289,29 @@ static int allreduce_op(Ctx& c, const double* in, double* out, int count, int op
 }
 
 // in must be red_loc (the in-process transport sums every member's red_loc)
-int allreduce_sum(Ctx& c, const double* in, double* out, int count) { return allreduce_op(c, in, out, count, 0); }
-int allreduce_max(Ctx& c, const double* in, double* out, int count) { return allreduce_op(c, in, out, count, 1); }
+static const double* const* red_ptrs(const Ctx& c) { return c.lg ? (const double* const*)c.lg->d_red_ptrs : nullptr; }
+static int red_fits(int count) {
+  if (count <= 16) return 0;
+  set_error("all-reduce: " + std::to_string(count) + " values do not fit red_loc (16)");
+  return 26;
+}
+int allreduce_sum(Ctx& c, const double* in, double* out, int count) {
+  if (int rc = red_fits(count)) return rc;
+  return allreduce_op(c, in, out, count, 0, red_ptrs(c));
+}
+int allreduce_max(Ctx& c, const double* in, double* out, int count) {
+  if (int rc = red_fits(count)) return rc;
+  return allreduce_op(c, in, out, count, 1, red_ptrs(c));
+}
+// the multigrid's sums that red_loc cannot hold (the coarsest operator's blocks, the coarsest
+// right-hand side): every rank's mg.arin, summed in rank order into out
+int allreduce_sum_mg(Ctx& c, double* out, int count) {
+  if (count > c.mg.ar_cap || (c.lg && !c.mg.d_ar_ptrs)) {
+    set_error("multigrid all-reduce: " + std::to_string(count) + " values, buffer of " + std::to_string(c.mg.ar_cap));
+    return 26;
+  }
+  return allreduce_op(c, c.mg.arin, out, count, 0, (const double* const*)c.mg.d_ar_ptrs);
+}
 
 // before overwriting red_loc: every member has summed the previous partials
 int allreduce_prepare(Ctx& c) {

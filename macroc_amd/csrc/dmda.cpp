@@ -186,9 +186,8 @@ int64_t count_nnz_rows(const Ctx& c, int64_t xs, int64_t ys, int64_t zs, int64_t
   return 9 * sum1(xs, nx, c.o.NX) * sum1(ys, ny, c.o.NY) * sum1(zs, nz, c.o.NZ);
 }
 
-void plan_halo(Ctx& c, std::vector<int>& sidx, std::vector<int>& ridx) {
-  HaloPlan& h = c.halo;
-  const Geo& g = c.g;
+void plan_halo(const Ctx& c, HaloPlan& h, const int n3[3], int PX, int PXY, std::vector<int>& sidx,
+               std::vector<int>& ridx) {
   h.nbr_rank.clear();
   h.send_off.clear();
   h.send_cnt.clear();
@@ -204,7 +203,7 @@ void plan_halo(Ctx& c, std::vector<int>& sidx, std::vector<int>& ridx) {
         if (qi < 0 || qj < 0 || qk < 0 || qi >= c.m || qj >= c.n || qk >= c.p) continue;
         int nr = qi + qj * c.m + qk * c.m * c.n;
         int lo[3], hi[3], glo[3], ghi[3];
-        int d3[3] = {dx, dy, dz}, n3[3] = {g.nx, g.ny, g.nz};
+        int d3[3] = {dx, dy, dz};
         for (int a = 0; a < 3; a++) {
           // padded coordinates: owned = 1..n, ghost = 0 and n+1
           if (d3[a] < 0) { lo[a] = 1; hi[a] = 2; glo[a] = 0; ghi[a] = 1; }
@@ -216,10 +215,10 @@ void plan_halo(Ctx& c, std::vector<int>& sidx, std::vector<int>& ridx) {
         h.recv_off.push_back((int64_t)ridx.size());
         for (int k = lo[2]; k < hi[2]; k++)
           for (int j = lo[1]; j < hi[1]; j++)
-            for (int i = lo[0]; i < hi[0]; i++) sidx.push_back(i + j * g.PX + k * g.PX * g.PY);
+            for (int i = lo[0]; i < hi[0]; i++) sidx.push_back(i + j * PX + k * PXY);
         for (int k = glo[2]; k < ghi[2]; k++)
           for (int j = glo[1]; j < ghi[1]; j++)
-            for (int i = glo[0]; i < ghi[0]; i++) ridx.push_back(i + j * g.PX + k * g.PX * g.PY);
+            for (int i = glo[0]; i < ghi[0]; i++) ridx.push_back(i + j * PX + k * PXY);
         h.send_cnt.push_back((int64_t)sidx.size() - h.send_off.back());
         h.recv_cnt.push_back((int64_t)ridx.size() - h.recv_off.back());
       }
@@ -237,10 +236,9 @@ int64_t pad_to_natural(const Ctx& c, int p) {
 // Box-stencil forward halo: for every existing neighbour direction, the owned boundary slab
 // is sent and the matching ghost slab of the padded box is received.  Both sides enumerate
 // their region k, j, i ascending, so the message needs no index exchange.
-int build_halo_plan(Ctx& c) {
-  HaloPlan& h = c.halo;
+int build_halo_plan(Ctx& c, HaloPlan& h, const int n3[3], int PX, int PXY, int64_t* bytes) {
   std::vector<int> sidx, ridx;
-  plan_halo(c, sidx, ridx);
+  plan_halo(c, h, n3, PX, PXY, sidx, ridx);
   if (h.nsend == 0) return 0;
   MCX_HIP(hipMalloc(&h.d_send_idx, sizeof(int) * h.nsend));
   MCX_HIP(hipMalloc(&h.d_recv_idx, sizeof(int) * h.nrecv));
@@ -248,21 +246,27 @@ int build_halo_plan(Ctx& c) {
   MCX_HIP(hipMalloc(&h.d_recvbuf, sizeof(double) * 3 * h.nrecv));
   MCX_HIP(hipMemcpy(h.d_send_idx, sidx.data(), sizeof(int) * h.nsend, hipMemcpyHostToDevice));
   MCX_HIP(hipMemcpy(h.d_recv_idx, ridx.data(), sizeof(int) * h.nrecv, hipMemcpyHostToDevice));
-  c.device_bytes += (int64_t)(sizeof(int) + 3 * sizeof(double)) * (h.nsend + h.nrecv);
+  *bytes += (int64_t)(sizeof(int) + 3 * sizeof(double)) * (h.nsend + h.nrecv);
   // the sent nodes once each, as owned indices (their p update runs before the exchange)
-  const Geo& g = c.g;
+  const int PY = PXY / PX;
   std::vector<int> bnd(sidx);
   std::sort(bnd.begin(), bnd.end());
   bnd.erase(std::unique(bnd.begin(), bnd.end()), bnd.end());
   for (int& p : bnd) {
-    const int pi = p % g.PX, pj = (p / g.PX) % g.PY, pk = p / (g.PX * g.PY);
-    p = (pi - 1) + (pj - 1) * g.nx + (pk - 1) * g.nx * g.ny;
+    const int pi = p % PX, pj = (p / PX) % PY, pk = p / PXY;
+    p = (pi - 1) + (pj - 1) * n3[0] + (pk - 1) * n3[0] * n3[1];
   }
   h.nbnd = (int64_t)bnd.size();
   MCX_HIP(hipMalloc(&h.d_bnd, sizeof(int) * h.nbnd));
   MCX_HIP(hipMemcpy(h.d_bnd, bnd.data(), sizeof(int) * h.nbnd, hipMemcpyHostToDevice));
-  c.device_bytes += (int64_t)sizeof(int) * h.nbnd;
+  *bytes += (int64_t)sizeof(int) * h.nbnd;
   return 0;
+}
+
+void free_halo_plan(HaloPlan& h) {
+  for (void* p : {(void*)h.d_send_idx, (void*)h.d_recv_idx, (void*)h.d_sendbuf, (void*)h.d_recvbuf, (void*)h.d_bnd})
+    if (p) (void)hipFree(p);
+  h = HaloPlan();
 }
 
 // Strain-displacement matrix of the unit reference hex at each Gauss point, the quantity

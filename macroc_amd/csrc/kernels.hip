@@ -6667,11 +6667,11 @@ __global__ void k_cg_logic(const double* __restrict__ red, int mode, CgState* cg
 // in-process all-reduce over the group members' buffers, in rank order (op 0 sum, 1 max)
 __global__ void k_group_sum(const double* const* __restrict__ ptrs, int nranks, int count, double* __restrict__ out,
                             int op) {
-  int v = threadIdx.x;
-  if (v >= count) return;
-  double s = op ? ptrs[0][v] : 0.;
-  for (int r = op ? 1 : 0; r < nranks; r++) s = op ? fmax(s, ptrs[r][v]) : s + ptrs[r][v];
-  out[v] = s;
+  for (int v = blockIdx.x * blockDim.x + threadIdx.x; v < count; v += gridDim.x * blockDim.x) {
+    double s = op ? ptrs[0][v] : 0.;
+    for (int r = op ? 1 : 0; r < nranks; r++) s = op ? fmax(s, ptrs[r][v]) : s + ptrs[r][v];
+    out[v] = s;
+  }
 }
 
 // reaction-force post-processing (src/forces.c:82-91, :145-155): per element of one boundary
@@ -6739,6 +6739,23 @@ __global__ void k_unpack(const int* __restrict__ idx, int64_t cnt, const double*
   const int p = idx[t];
 #pragma unroll
   for (int d = 0; d < 3; d++) pad[3 * (int64_t)p + d] = buf[3 * t + d];
+}
+
+// a multigrid level's box (pc_mg_dist): one thread per (node, component), cnt3 = 3 x nodes
+__global__ void k_pcmg_pack(const int* __restrict__ idx, int64_t cnt3, const double* __restrict__ pad,
+                            double* __restrict__ buf) {
+  const int64_t t = (int64_t)blockIdx.x * TPB + threadIdx.x;
+  if (t >= cnt3) return;
+  const int64_t q = t / 3;
+  buf[t] = pad[3 * (int64_t)idx[q] + (t - 3 * q)];
+}
+
+__global__ void k_pcmg_unpack(const int* __restrict__ idx, int64_t cnt3, const double* __restrict__ buf,
+                              double* __restrict__ pad) {
+  const int64_t t = (int64_t)blockIdx.x * TPB + threadIdx.x;
+  if (t >= cnt3) return;
+  const int64_t q = t / 3;
+  pad[3 * (int64_t)idx[q] + (t - 3 * q)] = buf[t];
 }
 
 // ============================================================================ launchers
@@ -8149,22 +8166,34 @@ void launch_copy_pad_to_owned(Ctx& c, const double* pad, double* owned) {
   hipLaunchKernelGGL(k_pad_to_owned, dim3(nblk(c.g.nown)), dim3(TPB), 0, c.stream, c.g, pad, owned);
 }
 
-void launch_pack(Ctx& c, const double* xpad) {
-  if (!c.halo.nsend) return;
-  hipLaunchKernelGGL(k_pack, dim3(nblk(c.halo.nsend)), dim3(TPB), 0, c.stream, c.halo.d_send_idx, c.halo.nsend, xpad,
-                     c.halo.d_sendbuf);
+// the context's plan: one thread per node (k_pack / k_unpack); a multigrid level's box (h.level >= 1):
+// one thread per (node, component)
+void launch_pack(Ctx& c, const HaloPlan& h, const double* xpad) {
+  if (!h.nsend) return;
+  if (h.level < 0)
+    hipLaunchKernelGGL(k_pack, dim3(nblk(h.nsend)), dim3(TPB), 0, c.stream, h.d_send_idx, h.nsend, xpad, h.d_sendbuf);
+  else
+    hipLaunchKernelGGL(k_pcmg_pack, dim3(nblk(3 * h.nsend)), dim3(TPB), 0, c.stream, h.d_send_idx, 3 * h.nsend, xpad,
+                       h.d_sendbuf);
 }
 
-void launch_unpack(Ctx& c, double* xpad) {
-  if (!c.halo.nrecv) return;
-  hipLaunchKernelGGL(k_unpack, dim3(nblk(c.halo.nrecv)), dim3(TPB), 0, c.stream, c.halo.d_recv_idx, c.halo.nrecv,
-                     c.halo.d_recvbuf, xpad);
+void launch_unpack(Ctx& c, const HaloPlan& h, double* xpad) {
+  if (!h.nrecv) return;
+  if (h.level < 0)
+    hipLaunchKernelGGL(k_unpack, dim3(nblk(h.nrecv)), dim3(TPB), 0, c.stream, h.d_recv_idx, h.nrecv, h.d_recvbuf, xpad);
+  else
+    hipLaunchKernelGGL(k_pcmg_unpack, dim3(nblk(3 * h.nrecv)), dim3(TPB), 0, c.stream, h.d_recv_idx, 3 * h.nrecv,
+                       h.d_recvbuf, xpad);
 }
 
 // reduce partials into out (and, for RED_NORM, out[0] = sqrt); multi-rank: local sums are
 // all-reduced over RCCL first.
 void launch_group_sum(Ctx& c, const double* const* ptrs, int nranks, int count, double* out, int op) {
-  hipLaunchKernelGGL(k_group_sum, dim3(1), dim3(64), 0, c.stream, ptrs, nranks, count, out, op);
+  if (count <= 64)
+    hipLaunchKernelGGL(k_group_sum, dim3(1), dim3(64), 0, c.stream, ptrs, nranks, count, out, op);
+  else  // the multigrid's coarsest level (pc_mg_dist)
+    hipLaunchKernelGGL(k_group_sum, dim3(std::min<unsigned>(nblk(count), 1024u)), dim3(TPB), 0, c.stream, ptrs, nranks,
+                       count, out, op);
 }
 
 void launch_vtu_cells(Ctx& c, const int* lo, const int* cnt, double* out) {
@@ -8492,7 +8521,8 @@ __global__ void k_pcmg_mask0(Geo g, unsigned char* __restrict__ mask) {
   mask[n] = (unsigned char)dirichlet_mask(g, g.xs + i, g.ys + j, g.zs + k);
 }
 
-__global__ __launch_bounds__(TPB) void k_pcmg_prolong(PcmgXfer t, PcmgLay lx, const double* __restrict__ xc, int probe,
+__global__ __launch_bounds__(TPB) void k_pcmg_prolong(PcmgXfer t, PcmgLay lx, PcmgLay lc, const double* __restrict__ xc,
+                                                      int probe,
                                                       const unsigned char* __restrict__ fmask,
                                                       double* __restrict__ xf, int add) {
   const int64_t nf = (int64_t)t.fn[0] * t.fn[1] * t.fn[2];
@@ -8500,8 +8530,9 @@ __global__ __launch_bounds__(TPB) void k_pcmg_prolong(PcmgXfer t, PcmgLay lx, co
   if (n >= nf) return;
   const int nq = (int)n, i = nq % t.fn[0], j = (nq / t.fn[0]) % t.fn[1], k = nq / (t.fn[0] * t.fn[1]);  // 32-bit divisions
   int ci, cj, ck;
-  const int mi = pcmg_parents(i, t.fn[0], t.cn[0], ci), mj = pcmg_parents(j, t.fn[1], t.cn[1], cj),
-            mk = pcmg_parents(k, t.fn[2], t.cn[2], ck);
+  // parents by the global index (ci, cj, ck: global coarse indices; one rank: the local ones)
+  const int mi = pcmg_parents(i + t.fs[0], t.FN[0], t.CN[0], ci), mj = pcmg_parents(j + t.fs[1], t.FN[1], t.CN[1], cj),
+            mk = pcmg_parents(k + t.fs[2], t.FN[2], t.CN[2], ck);
   const double wt = (mi == 2 ? .5 : 1.) * (mj == 2 ? .5 : 1.) * (mk == 2 ? .5 : 1.);
   const int pa = probe >= 0 ? (probe / 3) % 3 : 0, pb = probe >= 0 ? (probe / 9) % 3 : 0, pc = probe >= 0 ? probe / 27 : 0,
             pd = probe >= 0 ? probe % 3 : 0;
@@ -8513,7 +8544,7 @@ __global__ __launch_bounds__(TPB) void k_pcmg_prolong(PcmgXfer t, PcmgLay lx, co
         if (probe >= 0) {
           if (I % 3 == pa && J % 3 == pb && K % 3 == pc) v[pd] += wt;
         } else {
-          const int64_t q = 3 * (I + (int64_t)t.cn[0] * (J + (int64_t)t.cn[1] * K));
+          const int64_t q = 3 * pcmg_at(lc, I - t.cs[0], J - t.cs[1], K - t.cs[2]);
 #pragma unroll
           for (int d = 0; d < 3; d++) v[d] += wt * xc[q + d];
         }
@@ -8527,7 +8558,7 @@ __global__ __launch_bounds__(TPB) void k_pcmg_prolong(PcmgXfer t, PcmgLay lx, co
   }
 }
 
-__global__ __launch_bounds__(TPB) void k_pcmg_restrict(PcmgXfer t, const double* __restrict__ b,
+__global__ __launch_bounds__(TPB) void k_pcmg_restrict(PcmgXfer t, PcmgLay lb, const double* __restrict__ b,
                                                        const double* __restrict__ w,
                                                        const unsigned char* __restrict__ fmask,
                                                        double* __restrict__ bc) {
@@ -8536,17 +8567,25 @@ __global__ __launch_bounds__(TPB) void k_pcmg_restrict(PcmgXfer t, const double*
   if (n >= ncn) return;
   const int nq = (int)n, I = nq % t.cn[0], J = (nq / t.cn[0]) % t.cn[1], K = nq / (t.cn[0] * t.cn[1]);  // 32-bit divisions
   int fi[3], fj[3], fk[3];
-  const int mi = pcmg_children(I, t.fn[0], fi), mj = pcmg_children(J, t.fn[1], fj), mk = pcmg_children(K, t.fn[2], fk);
+  // children by the global index, then local to the rank's fine box (-1 and fn: its ghost layer)
+  const int mi = pcmg_children(I + t.cs[0], t.FN[0], fi), mj = pcmg_children(J + t.cs[1], t.FN[1], fj),
+            mk = pcmg_children(K + t.cs[2], t.FN[2], fk);
+  for (int a = 0; a < 3; a++) {
+    fi[a] -= t.fs[0];
+    fj[a] -= t.fs[1];
+    fk[a] -= t.fs[2];
+  }
   double acc[3] = {0., 0., 0.};
   for (int c = 0; c < mk; c++)
     for (int bb = 0; bb < mj; bb++)
       for (int a = 0; a < mi; a++) {
         const double wt = (a ? .5 : 1.) * (bb ? .5 : 1.) * (c ? .5 : 1.);
-        const int64_t f = fi[a] + (int64_t)t.fn[0] * (fj[bb] + (int64_t)t.fn[1] * fk[c]);
-        const int m = fmask[f];
+        const int64_t f = fi[a] + (int64_t)t.fn[0] * (fj[bb] + (int64_t)t.fn[1] * fk[c]);  // owned order (w, fmask)
+        const int64_t fb = 3 * pcmg_at(lb, fi[a], fj[bb], fk[c]);
+        const int m = fmask ? fmask[f] : 0;
 #pragma unroll
         for (int d = 0; d < 3; d++) {
-          const double rv = w ? b[3 * f + d] - w[3 * f + d] : b[3 * f + d];
+          const double rv = w ? b[fb + d] - w[3 * f + d] : b[fb + d];
           if (!(m >> d & 1)) acc[d] += wt * rv;
         }
       }
@@ -8555,9 +8594,10 @@ __global__ __launch_bounds__(TPB) void k_pcmg_restrict(PcmgXfer t, const double*
 }
 
 // r = b - A x (b null: r = A x) with A the level's 27 stencil blocks, slot-major
-__global__ __launch_bounds__(TPB) void k_pcmg_spmv(int nx, int ny, int nz, const double* __restrict__ A,
+__global__ __launch_bounds__(TPB) void k_pcmg_spmv(PcmgLay lx, const double* __restrict__ A,
                                                    const double* __restrict__ x, const double* __restrict__ b,
                                                    double* __restrict__ r) {
+  const int nx = lx.nx, ny = lx.ny, nz = lx.nz;
   const int64_t nn = (int64_t)nx * ny * nz;
   const int64_t n = (int64_t)blockIdx.x * TPB + threadIdx.x;
   if (n >= nn) return;
@@ -8565,8 +8605,11 @@ __global__ __launch_bounds__(TPB) void k_pcmg_spmv(int nx, int ny, int nz, const
   double acc[3] = {0., 0., 0.};
   for (int nb = 0; nb < 27; nb++) {
     const int ii = i + nb % 3 - 1, jj = j + (nb / 3) % 3 - 1, kk = k + nb / 9 - 1;
-    if (ii < 0 || jj < 0 || kk < 0 || ii >= nx || jj >= ny || kk >= nz) continue;
-    const int64_t m = 3 * (ii + (int64_t)nx * (jj + (int64_t)ny * kk));
+    // outside the global grid: no block; outside the rank's box: a ghost column of the padded box
+    if (ii + lx.gs[0] < 0 || jj + lx.gs[1] < 0 || kk + lx.gs[2] < 0 || ii + lx.gs[0] >= lx.gn[0] ||
+        jj + lx.gs[1] >= lx.gn[1] || kk + lx.gs[2] >= lx.gn[2])
+      continue;
+    const int64_t m = 3 * pcmg_at(lx, ii, jj, kk);
     const double x0 = x[m], x1 = x[m + 1], x2 = x[m + 2];
     const double* a = A + (int64_t)(nb * 9) * nn + n;
 #pragma unroll
@@ -8583,17 +8626,19 @@ __global__ __launch_bounds__(TPB) void k_pcmg_spmv(int nx, int ny, int nz, const
 // Galerkin probe: t = P^T A P e with e the indicator of colour (a, b, c) = (I, J, K) mod 3 and
 // component d.  Node J has at most one neighbour of that colour: t[J] is column d of the block
 // toward it.
-__global__ void k_pcmg_scatter(int nx, int ny, int nz, const double* __restrict__ t, double* __restrict__ A,
-                               int colour, int d) {
+__global__ void k_pcmg_scatter(PcmgLay lx, const double* __restrict__ t, double* __restrict__ A, int colour, int d) {
+  const int nx = lx.nx, ny = lx.ny, nz = lx.nz;
   const int64_t nn = (int64_t)nx * ny * nz;
   const int64_t n = (int64_t)blockIdx.x * TPB + threadIdx.x;
   if (n >= nn) return;
   const int nq = (int)n, i = nq % nx, j = (nq / nx) % ny, k = nq / (nx * ny);  // 32-bit divisions
-  int ox = (colour % 3 - i % 3 + 3) % 3, oy = ((colour / 3) % 3 - j % 3 + 3) % 3, oz = (colour / 9 - k % 3 + 3) % 3;
+  const int gi = i + lx.gs[0], gj = j + lx.gs[1], gk = k + lx.gs[2];  // colours go by the global index
+  int ox = (colour % 3 - gi % 3 + 3) % 3, oy = ((colour / 3) % 3 - gj % 3 + 3) % 3, oz = (colour / 9 - gk % 3 + 3) % 3;
   if (ox == 2) ox = -1;
   if (oy == 2) oy = -1;
   if (oz == 2) oz = -1;
-  if (i + ox < 0 || i + ox >= nx || j + oy < 0 || j + oy >= ny || k + oz < 0 || k + oz >= nz) return;
+  if (gi + ox < 0 || gi + ox >= lx.gn[0] || gj + oy < 0 || gj + oy >= lx.gn[1] || gk + oz < 0 || gk + oz >= lx.gn[2])
+    return;
   const int nb = (oz + 1) * 9 + (oy + 1) * 3 + (ox + 1);
 #pragma unroll
   for (int rr = 0; rr < 3; rr++) A[(int64_t)(nb * 9 + rr * 3 + d) * nn + n] = t[3 * n + rr];
@@ -8659,7 +8704,9 @@ __global__ void k_pcmg_seed(PcmgLay lx, int64_t nn, double* __restrict__ x) {
   const int64_t xq = 3 * pcmg_at(lx, i, j, k);
 #pragma unroll
   for (int d = 0; d < 3; d++) {
-    unsigned h = (unsigned)(3 * n + d) * 2654435761u;
+    // the node's global natural index (one rank: n), so a decomposed grid starts from the same vector
+    const int64_t gq = (i + lx.gs[0]) + (int64_t)lx.gn[0] * ((j + lx.gs[1]) + (int64_t)lx.gn[1] * (k + lx.gs[2]));
+    unsigned h = (unsigned)(3 * gq + d) * 2654435761u;
     h ^= h >> 15;
     h *= 2246822519u;
     h ^= h >> 13;
@@ -8739,27 +8786,99 @@ __global__ void k_pcmg_jacobi(int64_t n, const double* __restrict__ r, const dou
   if (q < n) z[q] = r[q] * dinv[q];
 }
 
-PcmgLay pcmg_lay_nat(const int n[3]) { return PcmgLay{n[0], n[1], n[2], n[0], n[0] * n[1], 0}; }
-PcmgLay pcmg_lay_pad(const Ctx& c) { return PcmgLay{c.g.nx, c.g.ny, c.g.nz, c.g.PX, c.g.PX * c.g.PY, 1}; }
+// pc_mg_dist: the masked residual in the padded box (its owner masks, then the ghosts are exchanged)
+__global__ void k_pcmg_resid(PcmgLay lx, int64_t nn, const double* __restrict__ b, const double* __restrict__ w,
+                             const unsigned char* __restrict__ mask, double* __restrict__ rp) {
+  const int64_t n = (int64_t)blockIdx.x * TPB + threadIdx.x;
+  if (n >= nn) return;
+  const int nq = (int)n, i = nq % lx.nx, j = (nq / lx.nx) % lx.ny, k = nq / (lx.nx * lx.ny);  // 32-bit divisions
+  const int64_t xq = 3 * pcmg_at(lx, i, j, k);
+  const int m = mask[n];
+#pragma unroll
+  for (int d = 0; d < 3; d++) {
+    const double rv = w ? b[3 * n + d] - w[3 * n + d] : b[3 * n + d];
+    rp[xq + d] = (m >> d & 1) ? 0. : rv;
+  }
+}
+
+// pc_mg_dist, the coarsest level: the rank's owned entries of the level's global vector (natural order)
+__global__ void k_pcmg_to_full(PcmgLay lx, int64_t nn, const double* __restrict__ v, double* __restrict__ full) {
+  const int64_t n = (int64_t)blockIdx.x * TPB + threadIdx.x;
+  if (n >= nn) return;
+  const int nq = (int)n, i = nq % lx.nx, j = (nq / lx.nx) % lx.ny, k = nq / (lx.nx * lx.ny);  // 32-bit divisions
+  const int64_t gq = (i + lx.gs[0]) + (int64_t)lx.gn[0] * ((j + lx.gs[1]) + (int64_t)lx.gn[1] * (k + lx.gs[2]));
+#pragma unroll
+  for (int d = 0; d < 3; d++) full[3 * gq + d] = v[3 * n + d];
+}
+
+// ... and back: the rank's padded box of the global vector, ghosts included, 0 outside the grid
+__global__ void k_pcmg_from_full(PcmgLay lx, const double* __restrict__ full, double* __restrict__ xpad) {
+  const int bx = lx.nx + 2, by = lx.ny + 2, bz = lx.nz + 2;
+  const int n = blockIdx.x * TPB + threadIdx.x;
+  if (n >= bx * by * bz) return;
+  const int i = n % bx - 1, j = (n / bx) % by - 1, k = n / (bx * by) - 1;
+  const int gi = i + lx.gs[0], gj = j + lx.gs[1], gk = k + lx.gs[2];
+  const bool in = gi >= 0 && gj >= 0 && gk >= 0 && gi < lx.gn[0] && gj < lx.gn[1] && gk < lx.gn[2];
+  const int64_t gq = gi + (int64_t)lx.gn[0] * (gj + (int64_t)lx.gn[1] * gk), xq = 3 * pcmg_at(lx, i, j, k);
+#pragma unroll
+  for (int d = 0; d < 3; d++) xpad[xq + d] = in ? full[3 * gq + d] : 0.;
+}
+
+// ... and the rank's operator blocks into the global slot-major array [243][NN]: one thread per (slot, node)
+__global__ void k_pcmg_blocks_to_full(PcmgLay lx, int64_t nn, const double* __restrict__ A, int64_t NN,
+                                      double* __restrict__ full) {
+  const int64_t t = (int64_t)blockIdx.x * TPB + threadIdx.x;
+  if (t >= 243 * nn) return;
+  const int64_t slot = t / nn;
+  const int nq = (int)(t - slot * nn), i = nq % lx.nx, j = (nq / lx.nx) % lx.ny, k = nq / (lx.nx * lx.ny);
+  const int64_t gq = (i + lx.gs[0]) + (int64_t)lx.gn[0] * ((j + lx.gs[1]) + (int64_t)lx.gn[1] * (k + lx.gs[2]));
+  full[slot * NN + gq] = A[t];
+}
+
+PcmgLay pcmg_lay_nat(const int n[3]) {
+  return PcmgLay{n[0], n[1], n[2], n[0], n[0] * n[1], 0, {0, 0, 0}, {n[0], n[1], n[2]}};
+}
+PcmgLay pcmg_lay_pad(const Ctx& c) {
+  return PcmgLay{c.g.nx, c.g.ny, c.g.nz, c.g.PX, c.g.PX * c.g.PY, 1, {c.g.xs, c.g.ys, c.g.zs}, {c.g.NX, c.g.NY, c.g.NZ}};
+}
+PcmgLay pcmg_lay_box(const PcmgLevel& v) {
+  return PcmgLay{v.n[0], v.n[1], v.n[2], v.n[0] + 2, (v.n[0] + 2) * (v.n[1] + 2), 1, {v.s[0], v.s[1], v.s[2]},
+                 {v.N[0], v.N[1], v.N[2]}};
+}
+void launch_pcmg_resid(Ctx& c, const PcmgLay& lx, int64_t nn, const double* b, const double* w, const unsigned char* mask,
+                       double* rp) {
+  hipLaunchKernelGGL(k_pcmg_resid, dim3(nblk(nn)), dim3(TPB), 0, c.stream, lx, nn, b, w, mask, rp);
+}
+void launch_pcmg_to_full(Ctx& c, const PcmgLay& lx, int64_t nn, const double* v, double* full) {
+  hipLaunchKernelGGL(k_pcmg_to_full, dim3(nblk(nn)), dim3(TPB), 0, c.stream, lx, nn, v, full);
+}
+void launch_pcmg_from_full(Ctx& c, const PcmgLay& lx, const double* full, double* xpad) {
+  const int64_t nb = (int64_t)(lx.nx + 2) * (lx.ny + 2) * (lx.nz + 2);
+  hipLaunchKernelGGL(k_pcmg_from_full, dim3(nblk(nb)), dim3(TPB), 0, c.stream, lx, full, xpad);
+}
+void launch_pcmg_blocks_to_full(Ctx& c, const PcmgLay& lx, int64_t nn, const double* A, int64_t NN, double* full) {
+  hipLaunchKernelGGL(k_pcmg_blocks_to_full, dim3(nblk(243 * nn)), dim3(TPB), 0, c.stream, lx, nn, A, NN, full);
+}
 
 void launch_pcmg_mask0(Ctx& c, unsigned char* mask) {
   hipLaunchKernelGGL(k_pcmg_mask0, dim3(nblk(c.g.nown)), dim3(TPB), 0, c.stream, c.g, mask);
 }
-void launch_pcmg_prolong(Ctx& c, const PcmgXfer& t, const PcmgLay& lx, const double* xc, int probe,
+void launch_pcmg_prolong(Ctx& c, const PcmgXfer& t, const PcmgLay& lx, const PcmgLay& lc, const double* xc, int probe,
                          const unsigned char* fmask, double* xf, bool add) {
   const int64_t nf = (int64_t)t.fn[0] * t.fn[1] * t.fn[2];
-  hipLaunchKernelGGL(k_pcmg_prolong, dim3(nblk(nf)), dim3(TPB), 0, c.stream, t, lx, xc, probe, fmask, xf, add ? 1 : 0);
+  hipLaunchKernelGGL(k_pcmg_prolong, dim3(nblk(nf)), dim3(TPB), 0, c.stream, t, lx, lc, xc, probe, fmask, xf,
+                     add ? 1 : 0);
 }
-void launch_pcmg_restrict(Ctx& c, const PcmgXfer& t, const double* b, const double* w, const unsigned char* fmask,
-                          double* bc) {
+void launch_pcmg_restrict(Ctx& c, const PcmgXfer& t, const PcmgLay& lb, const double* b, const double* w,
+                          const unsigned char* fmask, double* bc) {
   const int64_t ncn = (int64_t)t.cn[0] * t.cn[1] * t.cn[2];
-  hipLaunchKernelGGL(k_pcmg_restrict, dim3(nblk(ncn)), dim3(TPB), 0, c.stream, t, b, w, fmask, bc);
+  hipLaunchKernelGGL(k_pcmg_restrict, dim3(nblk(ncn)), dim3(TPB), 0, c.stream, t, lb, b, w, fmask, bc);
 }
-void launch_pcmg_spmv(Ctx& c, const PcmgLevel& l, const double* x, const double* b, double* r) {
-  hipLaunchKernelGGL(k_pcmg_spmv, dim3(nblk(l.nn)), dim3(TPB), 0, c.stream, l.n[0], l.n[1], l.n[2], l.A, x, b, r);
+void launch_pcmg_spmv(Ctx& c, const PcmgLevel& l, const PcmgLay& lx, const double* x, const double* b, double* r) {
+  hipLaunchKernelGGL(k_pcmg_spmv, dim3(nblk(l.nn)), dim3(TPB), 0, c.stream, lx, l.A, x, b, r);
 }
-void launch_pcmg_scatter(Ctx& c, const PcmgLevel& l, const double* t, int colour, int d) {
-  hipLaunchKernelGGL(k_pcmg_scatter, dim3(nblk(l.nn)), dim3(TPB), 0, c.stream, l.n[0], l.n[1], l.n[2], t, l.A, colour, d);
+void launch_pcmg_scatter(Ctx& c, const PcmgLevel& l, const PcmgLay& lx, const double* t, int colour, int d) {
+  hipLaunchKernelGGL(k_pcmg_scatter, dim3(nblk(l.nn)), dim3(TPB), 0, c.stream, lx, t, l.A, colour, d);
 }
 void launch_pcmg_diag(Ctx& c, const PcmgLevel& l) {
   hipLaunchKernelGGL(k_pcmg_diag, dim3(nblk(l.nn)), dim3(TPB), 0, c.stream, l.nn, l.A, l.dinv, l.mask);
@@ -8775,21 +8894,26 @@ void launch_pcmg_gemv(Ctx& c, int n, const double* ainv, const double* b, double
 void launch_pcmg_seed(Ctx& c, const PcmgLay& lx, int64_t nn, double* x) {
   hipLaunchKernelGGL(k_pcmg_seed, dim3(nblk(nn)), dim3(TPB), 0, c.stream, lx, nn, x);
 }
-// the partial sums of one value -> c.red[0] (k_reduce's fixed tree)
-static void pcmg_reduce(Ctx& c, int nparts) {
-  hipLaunchKernelGGL(k_reduce, dim3(1), dim3(1024), 0, c.stream, c.partials, nparts, 1, c.red, (int)RED_STORE, c.cg,
-                     c.hist, 0, c.cg);
+// the partial sums of one value -> c.red[0] (k_reduce's fixed tree); a context with a communicator:
+// the rank's sum, then the all-reduce in rank order
+static int pcmg_reduce(Ctx& c, int nparts) {
+  const bool multi = c.nranks > 1 || c.comm || c.lg;
+  if (multi)
+    if (int rc = allreduce_prepare(c)) return rc;
+  hipLaunchKernelGGL(k_reduce, dim3(1), dim3(1024), 0, c.stream, c.partials, nparts, 1, multi ? c.red_loc : c.red,
+                     (int)RED_STORE, c.cg, c.hist, 0, c.cg);
+  return multi ? allreduce_sum(c, c.red_loc, c.red, 1) : 0;
 }
-void launch_pcmg_scale_dot(Ctx& c, int64_t nn, const double* dinv, const double* w, double* y) {
+int launch_pcmg_scale_dot(Ctx& c, int64_t nn, const double* dinv, const double* w, double* y) {
   hipLaunchKernelGGL(k_pcmg_scale_dot, dim3(nblk(nn)), dim3(TPB), 0, c.stream, nn, dinv, w, y, c.partials);
-  pcmg_reduce(c, (int)nblk(nn));
+  return pcmg_reduce(c, (int)nblk(nn));
 }
 void launch_pcmg_scaleto(Ctx& c, const PcmgLay& lx, int64_t nn, const double* y, double s, double* x) {
   hipLaunchKernelGGL(k_pcmg_scaleto, dim3(nblk(nn)), dim3(TPB), 0, c.stream, lx, nn, y, s, x);
 }
-void launch_pcmg_dot(Ctx& c, const PcmgLay& la, int64_t nn, const double* a, const double* b) {
+int launch_pcmg_dot(Ctx& c, const PcmgLay& la, int64_t nn, const double* a, const double* b) {
   hipLaunchKernelGGL(k_pcmg_dot, dim3(nblk(nn)), dim3(TPB), 0, c.stream, la, nn, a, b, c.partials);
-  pcmg_reduce(c, (int)nblk(nn));
+  return pcmg_reduce(c, (int)nblk(nn));
 }
 void launch_pcmg_aypx(Ctx& c, int64_t n, const double* z, double bc, double* p, bool first) {
   hipLaunchKernelGGL(k_pcmg_aypx, dim3(nblk(n)), dim3(TPB), 0, c.stream, n, z, bc, p, first ? 1 : 0);

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../../include/macroc_amd.h"
+#include "pcmg_plan.h"
 
 namespace mcx {
 
@@ -124,19 +125,41 @@ struct MicroNlArgs {
 // -pc_type mg: geometric multigrid preconditioner of the macro CG, one rank.  Level 0
 // is the assembled matrix (launch_spmv, whatever its storage); a coarser level keeps its Galerkin
 // operator as plain stencil blocks, slot-major: value (nb, r, c) of node n at A[(nb*9 + r*3 + c) * nn + n].
-constexpr int PCMG_MAXLEV = 16;
-constexpr int PCMG_COARSE_MAX = 3072;  // dofs of the coarsest level (its inverse is dense)
-// where node (i, j, k) of a vector lives: (i + off) + (j + off) PX + (k + off) PXY.  Owned and coarse
-// vectors: PX = nx, PXY = nx ny, off = 0; the padded box of the fine level (the SpMV's input): off = 1
+// (PCMG_MAXLEV, PCMG_COARSE_MAX and the planner: pcmg_plan.h)
+// where node (i, j, k) of a rank's box lives in a vector: (i + off) + (j + off) PX + (k + off) PXY.
+// Owned and one-rank coarse vectors: PX = nx, PXY = nx ny, off = 0; a padded box (the fine level's SpMV
+// input; with pc_mg_dist every vector read through a stencil, P or P^T): off = 1.  gs / gn: the box's
+// global start and the level's global node counts (one rank: 0 and nx, ny, nz) — what decides by the
+// global index (coarse or not, the last-node rule, probe colours, the seed, the domain's edge) uses them.
 struct PcmgLay {
   int nx, ny, nz, PX, PXY, off;
+  int gs[3], gn[3];
 };
-struct PcmgXfer {  // node counts of a level and of the next coarser one
+struct PcmgXfer {  // a level and the next coarser one: owned counts, global starts, global counts
   int fn[3], cn[3];
+  int fs[3], cs[3], FN[3], CN[3];
 };
+struct HaloPlan {
+  std::vector<int> nbr_rank;          // neighbour ranks (<= 26)
+  std::vector<int64_t> send_off, send_cnt, recv_off, recv_cnt;  // in nodes
+  int* d_send_idx = nullptr;          // padded node index of each sent node
+  int* d_recv_idx = nullptr;          // padded node index of each received node
+  double* d_sendbuf = nullptr;
+  double* d_recvbuf = nullptr;
+  int64_t nsend = 0, nrecv = 0;
+  int* d_bnd = nullptr;               // owned node index of every sent node, each once
+  int64_t nbnd = 0;
+  int level = -1;                     // -1: the context's plan (Ctx::halo); l >= 1: multigrid level l's box (pc_mg_dist)
+};
+
 struct PcmgLevel {
-  int n[3] = {0, 0, 0};
-  int64_t nn = 0;              // nodes
+  int n[3] = {0, 0, 0};        // owned nodes of this rank's box
+  int64_t nn = 0;              // ... their product
+  int s[3] = {0, 0, 0};        // the box's global start
+  int N[3] = {0, 0, 0};        // the level's global node counts (one rank: n)
+  double* rp = nullptr;        // pc_mg_dist: the residual masked by its owner, padded box (what P^T reads after a halo)
+  void* rp_base = nullptr;     // ... its allocation on level 0 (aligned as x)
+  HaloPlan halo;               // pc_mg_dist, level >= 1: the box's ghost fill (level 0 uses Ctx::halo)
   double* A = nullptr;         // [243][nn] (levels >= 1)
   double* x = nullptr;         // the cycle's iterate (level 0: padded box, shifted by pad_off from x_base)
   void* x_base = nullptr;
@@ -148,22 +171,17 @@ struct Pcmg {
   int nlev = 0;
   PcmgLevel L[PCMG_MAXLEV];
   double* ainv = nullptr;      // dense inverse of the coarsest operator [nc][nc]
-  int nc = 0;                  // its dofs
+  int nc = 0;                  // its dofs (global)
+  // pc_mg_dist on a context with a communicator: every level's box per the plan, x and rp
+  // padded, and the coarsest level gathered by one all-reduce: arin (each rank's owned entries, zeros
+  // elsewhere) -> arout on every rank; xfull = Ainv arout, of which each rank keeps its box
+  bool dist = false;
+  double *arin = nullptr, *arout = nullptr, *xfull = nullptr;
+  int64_t ar_cap = 0;          // doubles of arin / arout (the coarsest operator's 243 NN blocks)
+  double** d_ar_ptrs = nullptr;  // in-process transport: every member's arin
   int64_t bytes = 0;           // device memory of the hierarchy (counted in Ctx::device_bytes)
   bool alloc = false;
   bool built = false;          // operators, eigenvalue estimates and the inverse belong to the current matrix
-};
-
-struct HaloPlan {
-  std::vector<int> nbr_rank;          // neighbour ranks (<= 26)
-  std::vector<int64_t> send_off, send_cnt, recv_off, recv_cnt;  // in nodes
-  int* d_send_idx = nullptr;          // padded node index of each sent node
-  int* d_recv_idx = nullptr;          // padded node index of each received node
-  double* d_sendbuf = nullptr;
-  double* d_recvbuf = nullptr;
-  int64_t nsend = 0, nrecv = 0;
-  int* d_bnd = nullptr;               // owned node index of every sent node, each once
-  int64_t nbnd = 0;
 };
 
 struct Ctx;
@@ -236,7 +254,7 @@ struct LocalGroup {
   std::string why;                 // ... and what it was
 };
 // barrier tags (which collective a crossing belongs to)
-enum { BAR_INIT = 1, BAR_HALO_PACKED, BAR_HALO_DONE, BAR_RED_IN, BAR_RED_SUM, BAR_FINALIZE, BAR_USER };
+enum { BAR_INIT = 1, BAR_HALO_PACKED, BAR_HALO_DONE, BAR_RED_IN, BAR_RED_SUM, BAR_FINALIZE, BAR_USER, BAR_MG_ALLOC };
 int group_barrier(LocalGroup* g, int rank, int tag, double timeout_s);  // 0, or 23 with the reason in mcx_last_error
 double comm_timeout_default();                       // MCX_COMM_TIMEOUT, default 300 s
 
@@ -487,6 +505,7 @@ struct Ctx {
 
   // options pc_type (0 Jacobi, 1 multigrid), pc_mg_levels (0: automatic), pc_mg_smooth (Chebyshev degree)
   int pc_type = 0, pc_mg_levels = 0, pc_mg_smooth = 2;
+  int pc_mg_dist = 0;  // option pc_mg_dist: 1 accepts pc_type 1 on a context with a communicator
   Pcmg mg;
 
   // external Gauss-point law (-mat_law external): host MicroPP-shaped callbacks or a device law
@@ -514,8 +533,11 @@ struct Ctx {
 int dmda_decide(int64_t M, int64_t N, int64_t P, int size, int* m, int* n, int* p);
 int setup_decomposition(Ctx& c);
 int64_t petsc_node(const Ctx& c, int64_t i, int64_t j, int64_t k);
-int build_halo_plan(Ctx& c);
-void plan_halo(Ctx& c, std::vector<int>& sidx, std::vector<int>& ridx);
+// the ghost fill of a box of n owned nodes in a padded vector of row pitch PX and plane pitch PXY
+// (the neighbours are the rank grid's); *bytes grows by the device memory taken
+int build_halo_plan(Ctx& c, HaloPlan& h, const int n[3], int PX, int PXY, int64_t* bytes);
+void free_halo_plan(HaloPlan& h);
+void plan_halo(const Ctx& c, HaloPlan& h, const int n[3], int PX, int PXY, std::vector<int>& sidx, std::vector<int>& ridx);
 int64_t pad_to_natural(const Ctx& c, int p);
 int64_t count_nnz_rows(const Ctx& c, int64_t xs, int64_t ys, int64_t zs, int64_t nx, int64_t ny, int64_t nz);
 void compute_B_table(double B[8][6][24]);
@@ -524,11 +546,17 @@ int64_t count_upper_values(const Ctx& c);
 // ---- communication (comm.cpp)
 int comm_init(Ctx& c, const void* id);
 void comm_destroy(Ctx& c);
-int halo_exchange(Ctx& c, double* xpad);   // halo_start + halo_finish
-int halo_start(Ctx& c, double* xpad);      // pack + exchange on the comm stream
-int halo_finish(Ctx& c, double* xpad);     // compute stream waits, unpacks
+int halo_exchange(Ctx& c, HaloPlan& h, double* xpad);   // halo_start + halo_finish
+int halo_start(Ctx& c, HaloPlan& h, double* xpad);      // pack + exchange on the comm stream
+int halo_finish(Ctx& c, HaloPlan& h, double* xpad);     // compute stream waits, unpacks
+// the context's own plan: its padded vectors (u, p, the multigrid's level 0)
+inline int halo_exchange(Ctx& c, double* xpad) { return halo_exchange(c, c.halo, xpad); }
+inline int halo_start(Ctx& c, double* xpad) { return halo_start(c, c.halo, xpad); }
+inline int halo_finish(Ctx& c, double* xpad) { return halo_finish(c, c.halo, xpad); }
 int allreduce_sum(Ctx& c, const double* in, double* out, int count);
 int allreduce_max(Ctx& c, const double* in, double* out, int count);
+// the multigrid's large sums (pc_mg_dist): in = mg.arin of every rank, up to mg.ar_cap doubles
+int allreduce_sum_mg(Ctx& c, double* out, int count);
 int allreduce_prepare(Ctx& c);
 // host wait for work that depends on other ranks (CG chunk polls, all-reduced norms): the RCCL
 // transport polls the event and the communicator's asynchronous error against c.comm_timeout and
@@ -574,8 +602,8 @@ void launch_reduce(Ctx& c, int nvals, int nparts, double* out);
 void launch_cg_init(Ctx& c);
 int cg_iteration(Ctx& c, hipEvent_t spmv_start, hipEvent_t spmv_stop, bool first, bool last);
 int cg_finish_init(Ctx& c);
-void launch_pack(Ctx& c, const double* xpad);
-void launch_unpack(Ctx& c, double* xpad);
+void launch_pack(Ctx& c, const HaloPlan& h, const double* xpad);
+void launch_unpack(Ctx& c, const HaloPlan& h, double* xpad);
 void launch_copy_owned_to_pad(Ctx& c, const double* owned, double* pad);
 void launch_copy_pad_to_owned(Ctx& c, const double* pad, double* owned);
 int64_t spmv_grid_blocks(const Ctx& c);
@@ -598,28 +626,43 @@ int dirichlet_mask_host(const Geo& g, int gi, int gj, int gk);
 // ---- -pc_type mg: kernels (kernels.hip) and the hierarchy, cycle and PCG loop (pcmg.cpp)
 void launch_pcmg_mask0(Ctx& c, unsigned char* mask);
 // xf (layout lx) = or += P xc; probe >= 0: xc is the indicator of colour probe / 3, component probe % 3
-void launch_pcmg_prolong(Ctx& c, const PcmgXfer& t, const PcmgLay& lx, const double* xc, int probe,
+// xc in layout lc
+void launch_pcmg_prolong(Ctx& c, const PcmgXfer& t, const PcmgLay& lx, const PcmgLay& lc, const double* xc, int probe,
                          const unsigned char* fmask, double* xf, bool add);
-void launch_pcmg_restrict(Ctx& c, const PcmgXfer& t, const double* b, const double* w, const unsigned char* fmask,
-                          double* bc);  // bc = P^T (b - w) (w may be null)
-void launch_pcmg_spmv(Ctx& c, const PcmgLevel& l, const double* x, const double* b, double* r);  // r = b - A x (b null: A x)
-void launch_pcmg_scatter(Ctx& c, const PcmgLevel& l, const double* t, int colour, int d);
+// bc = P^T (b - w), b in layout lb; w and fmask (owned order) may be null: pc_mg_dist hands over the
+// masked residual in a padded box, ghosts filled
+void launch_pcmg_restrict(Ctx& c, const PcmgXfer& t, const PcmgLay& lb, const double* b, const double* w,
+                          const unsigned char* fmask, double* bc);
+// r = b - A x (b null: A x), x in layout lx
+void launch_pcmg_spmv(Ctx& c, const PcmgLevel& l, const PcmgLay& lx, const double* x, const double* b, double* r);
+void launch_pcmg_scatter(Ctx& c, const PcmgLevel& l, const PcmgLay& lx, const double* t, int colour, int d);
+// pc_mg_dist: rp (layout lx, padded) = b - w (w null: b) with the level's Dirichlet dofs zeroed by their owner
+void launch_pcmg_resid(Ctx& c, const PcmgLay& lx, int64_t nn, const double* b, const double* w, const unsigned char* mask,
+                       double* rp);
+// pc_mg_dist, the coarsest level: owned vector -> its entries of the level's global vector; the global
+// vector -> the rank's padded box, ghosts included (0 outside the grid); owned operator blocks -> global [243][NN]
+void launch_pcmg_to_full(Ctx& c, const PcmgLay& lx, int64_t nn, const double* v, double* full);
+void launch_pcmg_from_full(Ctx& c, const PcmgLay& lx, const double* full, double* xpad);
+void launch_pcmg_blocks_to_full(Ctx& c, const PcmgLay& lx, int64_t nn, const double* A, int64_t NN, double* full);
 void launch_pcmg_diag(Ctx& c, const PcmgLevel& l);
 void launch_pcmg_cheb(Ctx& c, const PcmgLay& lx, int64_t nn, const double* b, const double* w, const double* dinv,
                       double* d, double* x, double ca, double cb, bool dfirst, bool xzero);
 void launch_pcmg_gemv(Ctx& c, int n, const double* ainv, const double* b, double* x);
 void launch_pcmg_seed(Ctx& c, const PcmgLay& lx, int64_t nn, double* x);
-void launch_pcmg_scale_dot(Ctx& c, int64_t nn, const double* dinv, const double* w, double* y);  // y = dinv w, c.red[0] = y.y
+int launch_pcmg_scale_dot(Ctx& c, int64_t nn, const double* dinv, const double* w, double* y);  // y = dinv w, c.red[0] = y.y (all ranks')
 void launch_pcmg_scaleto(Ctx& c, const PcmgLay& lx, int64_t nn, const double* y, double s, double* x);
-void launch_pcmg_dot(Ctx& c, const PcmgLay& la, int64_t nn, const double* a, const double* b);  // c.red[0] = a.b
+int launch_pcmg_dot(Ctx& c, const PcmgLay& la, int64_t nn, const double* a, const double* b);  // c.red[0] = a.b (all ranks')
 void launch_pcmg_aypx(Ctx& c, int64_t n, const double* z, double bc, double* p, bool first);  // p = z + bc p
 void launch_pcmg_xr(Ctx& c, const PcmgLay& lp, int64_t nn, double a, const double* p, const double* w, double* x,
                     double* r);  // x += a p, r -= a w
 void launch_pcmg_jacobi(Ctx& c, int64_t n, const double* r, const double* dinv, double* z);  // z = r dinv
 PcmgLay pcmg_lay_nat(const int n[3]);
 PcmgLay pcmg_lay_pad(const Ctx& c);
-int pcmg_dims(const Ctx& c, int levels, int* nlev, int n[][3]);  // the level sizes; levels 0: automatic
-int pcmg_check(Ctx& c, int levels);  // option check: one rank, the coarsest level of `levels` levels fits
+PcmgLay pcmg_lay_box(const PcmgLevel& v);  // level >= 1 under pc_mg_dist: the box plus one ghost layer
+bool pcmg_dist(const Ctx& c);  // pc_mg_dist on a context with a communicator: the distributed hierarchy
+int pcmg_dims(const Ctx& c, int levels, int* nlev, int n[][3]);  // the (global) level sizes; levels 0: automatic
+int pcmg_plan_ctx(const Ctx& c, int levels, PcmgPlan* P);  // the context's plan (one box per level), checked; 0 or 2
+int pcmg_check(Ctx& c, int levels);  // option check: one rank or pc_mg_dist, the levels exist, the coarsest one fits
 void pcmg_free(Ctx& c);
 int pcmg_ensure(Ctx& c);                                // build or rebuild the hierarchy for the current matrix
 int pcmg_apply(Ctx& c, const double* r_owned);          // mg.L[0].x (padded) = M^-1 r

@@ -11,74 +11,72 @@
 
 namespace mcx {
 
-// coarse node count of an axis with N nodes: the even indices, plus the last node when N - 1 is odd
-static int coarse_count(int N) { return N <= 2 ? N : (N - 1) / 2 + 1 + ((N - 1) & 1); }
+bool pcmg_dist(const Ctx& c) { return c.pc_mg_dist && (c.nranks > 1 || c.comm || c.lg); }
 
-// level sizes.  levels 0: stop once every axis has <= 5 nodes; otherwise that many levels, or fewer
-// when nothing coarsens any more.  Returns the dofs of the coarsest level.
+// the context's plan: one rank (or pc_mg_dist off) the whole grid, else the rank's box per level
+int pcmg_plan_ctx(const Ctx& c, int levels, PcmgPlan* P) {
+  const int N0[3] = {c.g.NX, c.g.NY, c.g.NZ};
+  const bool d = pcmg_dist(c);
+  const int mnp[3] = {d ? c.m : 1, d ? c.n : 1, d ? c.p : 1};
+  std::string err;
+  const int rc = pcmg_plan_checked(N0, mnp, d ? c.rank : 0, levels, P, &err);
+  if (rc) set_error(err);
+  return rc;
+}
+
+// the global level sizes.  levels 0: stop once every axis has <= 5 nodes (pc_mg_dist: or before a level
+// that leaves a rank without a node); otherwise that many levels, or fewer when nothing coarsens any
+// more.  Returns the dofs of the coarsest level.
 int pcmg_dims(const Ctx& c, int levels, int* nlev, int n[][3]) {
-  int cur[3] = {c.g.NX, c.g.NY, c.g.NZ}, L = 0;
-  const int want = levels > 0 ? levels : PCMG_MAXLEV;
-  while (true) {
-    for (int a = 0; a < 3; a++) n[L][a] = cur[a];
-    L++;
-    if (L >= want) break;
-    if (levels <= 0 && L >= 2 && cur[0] <= 5 && cur[1] <= 5 && cur[2] <= 5) break;
-    int nxt[3];
-    for (int a = 0; a < 3; a++) nxt[a] = coarse_count(cur[a]);
-    if (nxt[0] == cur[0] && nxt[1] == cur[1] && nxt[2] == cur[2]) break;
-    for (int a = 0; a < 3; a++) cur[a] = nxt[a];
+  const int N0[3] = {c.g.NX, c.g.NY, c.g.NZ};
+  const bool d = pcmg_dist(c);
+  const int mnp[3] = {d ? c.m : 1, d ? c.n : 1, d ? c.p : 1};
+  PcmgPlan P;
+  if (pcmg_plan(N0, mnp, d ? c.rank : 0, levels, &P, nullptr)) {  // refused level count: the fine level alone
+    P.nlev = 1;
+    for (int a = 0; a < 3; a++) P.N[0][a] = N0[a];
   }
-  *nlev = L;
-  return 3 * n[L - 1][0] * n[L - 1][1] * n[L - 1][2];
+  for (int l = 0; l < P.nlev; l++)
+    for (int a = 0; a < 3; a++) n[l][a] = P.N[l][a];
+  *nlev = P.nlev;
+  return 3 * n[P.nlev - 1][0] * n[P.nlev - 1][1] * n[P.nlev - 1][2];
 }
 
 // option check (pc_type 1 with the current pc_mg_levels): 0, or 2 with the reason
 int pcmg_check(Ctx& c, int levels) {
-  if (c.nranks > 1 || c.comm || c.lg) {
+  if ((c.nranks > 1 || c.comm || c.lg) && !c.pc_mg_dist) {
     set_error("pc_type mg: one rank only (this context is rank " + std::to_string(c.rank) + " of " +
-              std::to_string(c.nranks) + "); use -pc_type jacobi");
+              std::to_string(c.nranks) + "); use -pc_type jacobi, or set pc_mg_dist 1 first (-pc_mg_dist 1: the "
+              "distributed hierarchy)");
     return 2;
   }
-  int n[PCMG_MAXLEV][3], nl = 0;
-  pcmg_dims(c, levels, &nl, n);
-  const int64_t nc = 3 * (int64_t)n[nl - 1][0] * n[nl - 1][1] * n[nl - 1][2];
-  if (nl < 2) {
-    set_error("pc_type mg: the grid " + std::to_string(c.g.NX) + " x " + std::to_string(c.g.NY) + " x " +
-              std::to_string(c.g.NZ) + " has no coarser level");
-    return 2;
-  }
-  if (nc > PCMG_COARSE_MAX) {
-    int fit = 0;
-    for (int q = nl + 1; q <= PCMG_MAXLEV && !fit; q++) {
-      int m[PCMG_MAXLEV][3], ml = 0;
-      if (pcmg_dims(c, q, &ml, m) <= PCMG_COARSE_MAX) fit = ml;
-    }
-    set_error("pc_mg_levels " + std::to_string(levels) + ": the coarsest level " + std::to_string(n[nl - 1][0]) + " x " +
-              std::to_string(n[nl - 1][1]) + " x " + std::to_string(n[nl - 1][2]) + " has " + std::to_string(nc) +
-              " dofs, above the " + std::to_string(PCMG_COARSE_MAX) + " its dense inverse takes; " +
-              (fit ? std::to_string(fit) + " levels fit" : std::string("no level count fits")) + " (0: automatic)");
-    return 2;
-  }
-  return 0;
+  PcmgPlan P;
+  return pcmg_plan_ctx(c, levels, &P);
 }
 
 void pcmg_free(Ctx& c) {
   Pcmg& M = c.mg;
+  // in-process transport: a neighbour's stream may still copy from this rank's send buffers or sum its arin
+  if (M.dist && c.lg) (void)hipDeviceSynchronize();
   if (c.stream) (void)hipStreamSynchronize(c.stream);
+  if (c.comm_stream) (void)hipStreamSynchronize(c.comm_stream);
   for (int l = 0; l < PCMG_MAXLEV; l++) {
     PcmgLevel& v = M.L[l];
     if (v.x_base) (void)hipFree(v.x_base);
     else if (v.x) (void)hipFree(v.x);
+    if (v.rp_base) (void)hipFree(v.rp_base);
+    else if (v.rp) (void)hipFree(v.rp);
     void* own[] = {v.A, v.mask};
     for (void* p : own)
       if (p) (void)hipFree(p);
     if (l > 0)
       for (void* p : {(void*)v.b, (void*)v.r, (void*)v.d, (void*)v.dinv})
         if (p) (void)hipFree(p);
+    free_halo_plan(v.halo);
     v = PcmgLevel();
   }
-  if (M.ainv) (void)hipFree(M.ainv);
+  for (void* p : {(void*)M.ainv, (void*)M.arin, (void*)M.arout, (void*)M.xfull, (void*)M.d_ar_ptrs})
+    if (p) (void)hipFree(p);
   c.device_bytes -= M.bytes;
   M = Pcmg();
 }
@@ -87,23 +85,29 @@ template <class T>
 static int mg_alloc(Ctx& c, T** p, int64_t n) {
   MCX_HIP(hipMalloc((void**)p, sizeof(T) * (size_t)n));
   MCX_HIP(hipMemsetAsync(*p, 0, sizeof(T) * (size_t)n, c.stream));
-  c.mg.bytes += (int64_t)sizeof(T) * n;
+  c.mg.bytes += (int64_t)sizeof(T) * n;  // counted at once: pcmg_free subtracts what a failed allocation got
+  c.device_bytes += (int64_t)sizeof(T) * n;
   return 0;
 }
 
 static int pcmg_alloc(Ctx& c) {
   Pcmg& M = c.mg;
   if (M.alloc) return 0;
+  PcmgPlan P;
   int rc = pcmg_check(c, c.pc_mg_levels);
-  if (rc) return rc;
-  int n[PCMG_MAXLEV][3];
-  pcmg_dims(c, c.pc_mg_levels, &M.nlev, n);
+  if (rc || (rc = pcmg_plan_ctx(c, c.pc_mg_levels, &P))) return rc;
+  M.nlev = P.nlev;
+  M.dist = pcmg_dist(c);
   M.bytes = 0;
   M.alloc = true;  // pcmg_free releases whatever a failed allocation leaves
   for (int l = 0; l < M.nlev; l++) {
     PcmgLevel& v = M.L[l];
-    for (int a = 0; a < 3; a++) v.n[a] = n[l][a];
-    v.nn = (int64_t)n[l][0] * n[l][1] * n[l][2];
+    for (int a = 0; a < 3; a++) {
+      v.n[a] = P.n[l][a];
+      v.s[a] = P.s[l][a];
+      v.N[a] = P.N[l][a];
+    }
+    v.nn = (int64_t)v.n[0] * v.n[1] * v.n[2];
     if ((rc = mg_alloc(c, &v.mask, v.nn))) return rc;
     if (l == 0) {  // the iterate in the padded box (the SpMV's input), aligned as u and p are
       const int64_t npad = (int64_t)c.g.PX * c.g.PY * c.g.PZ * 3;
@@ -111,19 +115,43 @@ static int pcmg_alloc(Ctx& c) {
       if ((rc = mg_alloc(c, &base, (int64_t)sizeof(double) * npad + 256))) return rc;
       v.x_base = base;
       v.x = reinterpret_cast<double*>(base + c.pad_off);
+      if (M.dist) {
+        if ((rc = mg_alloc(c, &base, (int64_t)sizeof(double) * npad + 256))) return rc;
+        v.rp_base = base;
+        v.rp = reinterpret_cast<double*>(base + c.pad_off);
+      }
       v.r = c.w;
       v.d = c.z;
       v.dinv = c.dinv;
       launch_pcmg_mask0(c, v.mask);
-    } else if ((rc = mg_alloc(c, &v.A, 243 * v.nn)) || (rc = mg_alloc(c, &v.x, 3 * v.nn)) ||
-               (rc = mg_alloc(c, &v.b, 3 * v.nn)) || (rc = mg_alloc(c, &v.r, 3 * v.nn)) ||
-               (rc = mg_alloc(c, &v.d, 3 * v.nn)) || (rc = mg_alloc(c, &v.dinv, 3 * v.nn))) {
-      return rc;
+    } else {
+      const int64_t nbox = M.dist ? (int64_t)(v.n[0] + 2) * (v.n[1] + 2) * (v.n[2] + 2) : v.nn;
+      if ((rc = mg_alloc(c, &v.A, 243 * v.nn)) || (rc = mg_alloc(c, &v.x, 3 * nbox)) ||
+          (rc = mg_alloc(c, &v.b, 3 * v.nn)) || (rc = mg_alloc(c, &v.r, 3 * v.nn)) ||
+          (rc = mg_alloc(c, &v.d, 3 * v.nn)) || (rc = mg_alloc(c, &v.dinv, 3 * v.nn)))
+        return rc;
+      if (M.dist) {
+        if ((rc = mg_alloc(c, &v.rp, 3 * nbox))) return rc;
+        v.halo.level = l;
+        int64_t hb = 0;
+        rc = build_halo_plan(c, v.halo, v.n, v.n[0] + 2, (v.n[0] + 2) * (v.n[1] + 2), &hb);
+        M.bytes += hb;
+        c.device_bytes += hb;
+        if (rc) return rc;
+      }
     }
   }
-  M.nc = (int)(3 * M.L[M.nlev - 1].nn);
+  const PcmgLevel& last = M.L[M.nlev - 1];
+  const int64_t NN = (int64_t)last.N[0] * last.N[1] * last.N[2];
+  M.nc = (int)(3 * NN);
   if ((rc = mg_alloc(c, &M.ainv, (int64_t)M.nc * M.nc))) return rc;
-  c.device_bytes += M.bytes;
+  if (M.dist) {
+    M.ar_cap = 243 * NN;
+    if ((rc = mg_alloc(c, &M.arin, M.ar_cap)) || (rc = mg_alloc(c, &M.arout, M.ar_cap)) ||
+        (rc = mg_alloc(c, &M.xfull, (int64_t)M.nc)))
+      return rc;
+    if (c.lg && (rc = mg_alloc(c, &M.d_ar_ptrs, (int64_t)c.lg->nranks))) return rc;
+  }
   return 0;
 }
 
@@ -132,10 +160,28 @@ static PcmgXfer xfer(const Pcmg& M, int l) {
   for (int a = 0; a < 3; a++) {
     t.fn[a] = M.L[l].n[a];
     t.cn[a] = M.L[l + 1].n[a];
+    t.fs[a] = M.L[l].s[a];
+    t.cs[a] = M.L[l + 1].s[a];
+    t.FN[a] = M.L[l].N[a];
+    t.CN[a] = M.L[l + 1].N[a];
   }
   return t;
 }
-static PcmgLay lay_of(const Ctx& c, int l) { return l == 0 ? pcmg_lay_pad(c) : pcmg_lay_nat(c.mg.L[l].n); }
+// the layout of level l's iterate (and, pc_mg_dist, of its masked residual): padded wherever ghosts are read
+static PcmgLay lay_of(const Ctx& c, int l) {
+  if (l == 0) return pcmg_lay_pad(c);
+  return c.mg.dist ? pcmg_lay_box(c.mg.L[l]) : pcmg_lay_nat(c.mg.L[l].n);
+}
+// owned order of level l's box
+static PcmgLay lay_own(const Ctx& c, int l) {
+  const PcmgLevel& v = c.mg.L[l];
+  PcmgLay y = pcmg_lay_nat(v.n);
+  for (int a = 0; a < 3; a++) {
+    y.gs[a] = v.s[a];
+    y.gn[a] = v.N[a];
+  }
+  return y;
+}
 
 // c.red[0 .. n) on the host, after a bounded wait (the stream may hold collectives)
 static int read_red(Ctx& c, int n, double* out) {
@@ -148,28 +194,90 @@ static int read_red(Ctx& c, int n, double* out) {
   return 0;
 }
 
-// level l's operator on its iterate: r = b - A x (b null: A x) in v.r
-static void apply_level(Ctx& c, int l, const double* b) {
-  PcmgLevel& v = c.mg.L[l];
-  if (l == 0) launch_spmv(c, v.x, v.r, false, false);  // v.r = A x; the callers subtract
-  else launch_pcmg_spmv(c, v, v.x, b, v.r);
+// pc_mg_dist: fill the ghosts of a padded vector of level l
+static int ghosts(Ctx& c, int l, double* xpad) {
+  if (!c.mg.dist) return 0;
+  return l == 0 ? halo_exchange(c, c.halo, xpad) : halo_exchange(c, c.mg.L[l].halo, xpad);
 }
 
-// dense inverse of the coarsest operator: Cholesky A = L L^T on the host, then A^-1 = L^-T L^-1
+// level l's operator on its iterate: r = b - A x (b null: A x) in v.r
+static int apply_level(Ctx& c, int l, const double* b) {
+  PcmgLevel& v = c.mg.L[l];
+  if (int rc = ghosts(c, l, v.x)) return rc;
+  if (l == 0) launch_spmv(c, v.x, v.r, false, false);  // v.r = A x; the callers subtract
+  else launch_pcmg_spmv(c, v, lay_of(c, l), v.x, b, v.r);
+  return 0;
+}
+
+// L[l + 1].b = P^T (b - w) with level l's Dirichlet dofs masked (w null: P^T b).  pc_mg_dist: the owner
+// masks the residual into the padded box, one exchange fills its ghosts, P^T reads them
+static int restrict_level(Ctx& c, int l, const double* b, const double* w) {
+  Pcmg& M = c.mg;
+  PcmgLevel& v = M.L[l];
+  const PcmgXfer t = xfer(M, l);
+  if (!M.dist) {
+    launch_pcmg_restrict(c, t, lay_own(c, l), b, w, v.mask, M.L[l + 1].b);
+    return 0;
+  }
+  const PcmgLay lp = lay_of(c, l);
+  launch_pcmg_resid(c, lp, v.nn, b, w, v.mask, v.rp);
+  if (int rc = ghosts(c, l, v.rp)) return rc;
+  launch_pcmg_restrict(c, t, lp, v.rp, nullptr, nullptr, M.L[l + 1].b);
+  return 0;
+}
+
+// pc_mg_dist: something that can fail on one rank alone, agreed before the next collective: every
+// rank learns whether any rank failed (one all-reduced maximum)
+static int agree(Ctx& c, int rc, const char* what) {
+  const std::string e = rc ? std::string(mcx_last_error()) : std::string();
+  int r2 = allreduce_prepare(c);
+  if (r2) return r2;
+  const double flag = rc ? 1. : 0.;
+  MCX_HIP(hipMemcpyAsync(c.red_loc, &flag, sizeof(double), hipMemcpyHostToDevice, c.stream));
+  MCX_HIP(hipStreamSynchronize(c.stream));  // flag is a stack variable
+  if ((r2 = allreduce_max(c, c.red_loc, c.red, 1))) return r2;
+  double any = 0.;
+  if ((r2 = read_red(c, 1, &any))) return r2;
+  if (rc) {
+    set_error(e);
+    return rc;
+  }
+  if (any != 0.) {
+    set_error(std::string("pc_type mg: ") + what + " failed on another rank");
+    return 27;
+  }
+  return 0;
+}
+
+// dense inverse of the coarsest operator: Cholesky A = L L^T on the host, then A^-1 = L^-T L^-1.
+// pc_mg_dist: every rank contributes its owned blocks, one all-reduce gives every rank the whole
+// operator, and every rank factors it alike
 static int coarse_inverse(Ctx& c) {
   Pcmg& M = c.mg;
   const PcmgLevel& v = M.L[M.nlev - 1];
   const int n = M.nc;
-  const int64_t nn = v.nn;
+  const int64_t nn = (int64_t)v.N[0] * v.N[1] * v.N[2];
   std::vector<double> blk((size_t)243 * nn), A((size_t)n * n, 0.);
-  MCX_HIP(hipMemcpyAsync(blk.data(), v.A, sizeof(double) * blk.size(), hipMemcpyDeviceToHost, c.stream));
-  MCX_HIP(hipStreamSynchronize(c.stream));
+  if (M.dist) {
+    int rc = allreduce_prepare(c);
+    if (rc) return rc;
+    MCX_HIP(hipMemsetAsync(M.arin, 0, sizeof(double) * 243 * nn, c.stream));
+    launch_pcmg_blocks_to_full(c, lay_own(c, M.nlev - 1), v.nn, v.A, nn, M.arin);
+    if ((rc = allreduce_sum_mg(c, M.arout, (int)(243 * nn)))) return rc;
+    MCX_HIP(hipMemcpyAsync(blk.data(), M.arout, sizeof(double) * blk.size(), hipMemcpyDeviceToHost, c.stream));
+    MCX_HIP(hipEventRecord(c.ev_chunk[0], c.stream));
+    if ((rc = comm_wait(c, c.ev_chunk[0], "multigrid coarsest operator (all-reduced blocks)"))) return rc;
+    MCX_HIP(hipStreamSynchronize(c.stream));
+  } else {
+    MCX_HIP(hipMemcpyAsync(blk.data(), v.A, sizeof(double) * blk.size(), hipMemcpyDeviceToHost, c.stream));
+    MCX_HIP(hipStreamSynchronize(c.stream));
+  }
   for (int64_t p = 0; p < nn; p++) {
-    const int i = (int)(p % v.n[0]), j = (int)((p / v.n[0]) % v.n[1]), k = (int)(p / ((int64_t)v.n[0] * v.n[1]));
+    const int i = (int)(p % v.N[0]), j = (int)((p / v.N[0]) % v.N[1]), k = (int)(p / ((int64_t)v.N[0] * v.N[1]));
     for (int nb = 0; nb < 27; nb++) {
       const int ii = i + nb % 3 - 1, jj = j + (nb / 3) % 3 - 1, kk = k + nb / 9 - 1;
-      if (ii < 0 || jj < 0 || kk < 0 || ii >= v.n[0] || jj >= v.n[1] || kk >= v.n[2]) continue;
-      const int64_t q = ii + (int64_t)v.n[0] * (jj + (int64_t)v.n[1] * kk);
+      if (ii < 0 || jj < 0 || kk < 0 || ii >= v.N[0] || jj >= v.N[1] || kk >= v.N[2]) continue;
+      const int64_t q = ii + (int64_t)v.N[0] * (jj + (int64_t)v.N[1] * kk);
       for (int r = 0; r < 3; r++)
         for (int cc = 0; cc < 3; cc++) A[(size_t)(3 * p + r) * n + 3 * q + cc] = blk[(size_t)(nb * 9 + r * 3 + cc) * nn + p];
     }
@@ -227,13 +335,26 @@ static int coarse_inverse(Ctx& c) {
 
 int pcmg_ensure(Ctx& c) {
   Pcmg& M = c.mg;
+  const bool fresh = !M.alloc;
   int rc = pcmg_alloc(c);
+  if (fresh && pcmg_dist(c) && (!rc || M.alloc)) {
+    // every member has allocated its hierarchy (or failed to) before anyone exchanges with it, and
+    // every rank learns of a failure before the first collective of the set-up
+    if (c.lg) {
+      const std::string e = rc ? std::string(mcx_last_error()) : std::string();
+      if (int r2 = group_barrier(c.lg, c.rank, BAR_MG_ALLOC, c.comm_timeout)) return r2;
+      if (rc) set_error(e);
+    }
+    rc = agree(c, rc, "the allocation of the hierarchy");
+    if (!rc && c.lg) {
+      std::vector<double*> ptrs(c.lg->nranks);
+      for (int q = 0; q < c.lg->nranks; q++) ptrs[q] = c.lg->members[q]->mg.arin;
+      MCX_HIP(hipMemcpy(M.d_ar_ptrs, ptrs.data(), sizeof(double*) * ptrs.size(), hipMemcpyHostToDevice));
+    }
+  }
   if (rc) {
     const std::string e = mcx_last_error();
-    if (M.alloc) {
-      c.device_bytes += M.bytes;  // pcmg_free subtracts what was counted: a failed allocation counted nothing yet
-      pcmg_free(c);
-    }
+    if (M.alloc) pcmg_free(c);
     set_error(e);
     return rc;
   }
@@ -243,15 +364,14 @@ int pcmg_ensure(Ctx& c) {
   for (int l = 0; l + 1 < M.nlev; l++) {
     PcmgLevel &f = M.L[l], &k = M.L[l + 1];
     const PcmgXfer t = xfer(M, l);
-    const PcmgLay lx = lay_of(c, l);
+    const PcmgLay lx = lay_of(c, l), lc = lay_of(c, l + 1);
     MCX_HIP(hipMemsetAsync(k.A, 0, sizeof(double) * 243 * k.nn, c.stream));
     for (int colour = 0; colour < 27; colour++) {
-      if (colour % 3 >= k.n[0] || (colour / 3) % 3 >= k.n[1] || colour / 9 >= k.n[2]) continue;  // no node has it
+      if (colour % 3 >= k.N[0] || (colour / 3) % 3 >= k.N[1] || colour / 9 >= k.N[2]) continue;  // no node has it
       for (int d = 0; d < 3; d++) {
-        launch_pcmg_prolong(c, t, lx, nullptr, colour * 3 + d, f.mask, f.x, false);
-        apply_level(c, l, nullptr);
-        launch_pcmg_restrict(c, t, f.r, nullptr, f.mask, k.b);
-        launch_pcmg_scatter(c, k, k.b, colour, d);
+        launch_pcmg_prolong(c, t, lx, lc, nullptr, colour * 3 + d, f.mask, f.x, false);
+        if ((rc = apply_level(c, l, nullptr)) || (rc = restrict_level(c, l, f.r, nullptr))) return rc;
+        launch_pcmg_scatter(c, k, lay_own(c, l + 1), k.b, colour, d);
       }
     }
     launch_pcmg_diag(c, k);
@@ -263,8 +383,7 @@ int pcmg_ensure(Ctx& c) {
     launch_pcmg_seed(c, lx, v.nn, v.x);
     double nrm = 0.;
     for (int it = 0; it < 10; it++) {
-      apply_level(c, l, nullptr);
-      launch_pcmg_scale_dot(c, v.nn, v.dinv, v.r, v.d);
+      if ((rc = apply_level(c, l, nullptr)) || (rc = launch_pcmg_scale_dot(c, v.nn, v.dinv, v.r, v.d))) return rc;
       double s = 0.;
       if ((rc = read_red(c, 1, &s))) return rc;
       nrm = std::sqrt(s);
@@ -286,7 +405,7 @@ int pcmg_ensure(Ctx& c) {
 
 // Chebyshev of degree k on D^-1 A over [0.1, 1.1] lmax (the recurrence of PETSc's KSPCHEBYSHEV,
 // written for the increment d = x_new - x)
-static void smooth(Ctx& c, int l, const double* b, bool xzero) {
+static int smooth(Ctx& c, int l, const double* b, bool xzero) {
   PcmgLevel& v = c.mg.L[l];
   const PcmgLay lx = lay_of(c, l);
   const double emin = .1 * v.lmax, emax = 1.1 * v.lmax;
@@ -294,7 +413,8 @@ static void smooth(Ctx& c, int l, const double* b, bool xzero) {
   double ckm1 = 1., ck = mu;
   for (int s = 0; s < c.pc_mg_smooth; s++) {
     const bool skip = xzero && s == 0;  // x = 0: the residual is b
-    if (!skip) apply_level(c, l, b);
+    if (!skip)
+      if (int rc = apply_level(c, l, b)) return rc;
     // level 0: v.r = A x, the kernel subtracts; coarser levels: v.r = b - A x already
     const double* rb = skip || l == 0 ? b : v.r;
     const double* rw = !skip && l == 0 ? v.r : nullptr;
@@ -307,30 +427,43 @@ static void smooth(Ctx& c, int l, const double* b, bool xzero) {
       ck = ckp1;
     }
   }
+  return 0;
 }
 
-static void cycle(Ctx& c, int l, const double* b) {
+// One V-cycle.  pc_mg_dist adds, per smoothed level, one ghost fill before every operator
+// application, one of the masked residual before P^T and one of the coarse correction before P; the
+// coarsest level is one all-reduce of its right-hand side, the dense product on every rank, and each
+// rank's box of the result, ghosts included
+static int cycle(Ctx& c, int l, const double* b) {
   Pcmg& M = c.mg;
   PcmgLevel& v = M.L[l];
+  int rc = 0;
   if (l == M.nlev - 1) {
-    launch_pcmg_gemv(c, M.nc, M.ainv, b, v.x);
-    return;
+    if (!M.dist) {
+      launch_pcmg_gemv(c, M.nc, M.ainv, b, v.x);
+      return 0;
+    }
+    if ((rc = allreduce_prepare(c))) return rc;  // every rank has summed the previous arin
+    MCX_HIP(hipMemsetAsync(M.arin, 0, sizeof(double) * M.nc, c.stream));
+    launch_pcmg_to_full(c, lay_own(c, l), v.nn, b, M.arin);
+    if ((rc = allreduce_sum_mg(c, M.arout, M.nc))) return rc;
+    launch_pcmg_gemv(c, M.nc, M.ainv, M.arout, M.xfull);
+    launch_pcmg_from_full(c, lay_of(c, l), M.xfull, v.x);
+    return 0;
   }
-  smooth(c, l, b, true);
-  apply_level(c, l, b);
+  if ((rc = smooth(c, l, b, true)) || (rc = apply_level(c, l, b))) return rc;
   const PcmgXfer t = xfer(M, l);
-  if (l == 0) launch_pcmg_restrict(c, t, b, v.r, v.mask, M.L[1].b);
-  else launch_pcmg_restrict(c, t, v.r, nullptr, v.mask, M.L[l + 1].b);
-  cycle(c, l + 1, M.L[l + 1].b);
-  launch_pcmg_prolong(c, t, lay_of(c, l), M.L[l + 1].x, -1, v.mask, v.x, true);
-  smooth(c, l, b, false);
+  if ((rc = l == 0 ? restrict_level(c, l, b, v.r) : restrict_level(c, l, v.r, nullptr))) return rc;
+  if ((rc = cycle(c, l + 1, M.L[l + 1].b))) return rc;
+  if (l + 1 < M.nlev - 1 && (rc = ghosts(c, l + 1, M.L[l + 1].x))) return rc;  // the coarsest level left its ghosts
+  launch_pcmg_prolong(c, t, lay_of(c, l), lay_of(c, l + 1), M.L[l + 1].x, -1, v.mask, v.x, true);
+  return smooth(c, l, b, false);
 }
 
 int pcmg_apply(Ctx& c, const double* r_owned) {
   int rc = pcmg_ensure(c);
   if (rc) return rc;
-  cycle(c, 0, r_owned);
-  return 0;
+  return cycle(c, 0, r_owned);
 }
 
 // PCG around the V-cycle: KSPSolve_CG's steps and reasons with the norm sqrt(r . z), the two
@@ -356,8 +489,7 @@ int pcmg_solve(Ctx& c, int* its_out, double* rnorm, int* reason_out) {
   };
   MCX_HIP(hipMemsetAsync(c.du, 0, sizeof(double) * nown3, c.stream));
   MCX_HIP(hipMemcpyAsync(c.r, c.b, sizeof(double) * nown3, hipMemcpyDeviceToDevice, c.stream));
-  cycle(c, 0, c.r);
-  launch_pcmg_dot(c, lp, g.nown, z, c.r);
+  if ((rc = cycle(c, 0, c.r)) || (rc = launch_pcmg_dot(c, lp, g.nown, z, c.r))) return rc;
   double beta = 0., betaold = 0., dpi = 0., dpiold = 0.;
   if ((rc = read_red(c, 1, &beta))) return rc;
   double dp = std::sqrt(beta);
@@ -376,8 +508,9 @@ int pcmg_solve(Ctx& c, int* its_out, double* rnorm, int* reason_out) {
       break;
     }
     launch_pcmg_aypx(c, npad3, z, i > 0 ? beta / betaold : 0., c.p_pad, i == 0);
+    if (c.mg.dist && (rc = halo_exchange(c, c.p_pad))) return rc;  // z's ghosts are stale: p's are filled here
     launch_spmv(c, c.p_pad, c.w, false, false);
-    launch_pcmg_dot(c, lp, g.nown, c.p_pad, c.w);
+    if ((rc = launch_pcmg_dot(c, lp, g.nown, c.p_pad, c.w))) return rc;
     dpiold = dpi;
     if ((rc = read_red(c, 1, &dpi))) return rc;
     betaold = beta;
@@ -387,8 +520,7 @@ int pcmg_solve(Ctx& c, int* its_out, double* rnorm, int* reason_out) {
     }
     const double a = beta / dpi;
     launch_pcmg_xr(c, lp, g.nown, a, c.p_pad, c.w, c.du, c.r);
-    cycle(c, 0, c.r);
-    launch_pcmg_dot(c, lp, g.nown, z, c.r);
+    if ((rc = cycle(c, 0, c.r)) || (rc = launch_pcmg_dot(c, lp, g.nown, z, c.r))) return rc;
     if ((rc = read_red(c, 1, &beta))) return rc;
     if (beta < 0.) {
       reason = MCX_KSP_DIVERGED_INDEFINITE_PC;
