@@ -406,7 +406,11 @@ int mcx_dump_csr(void* ctx, int64_t* rowptr, int64_t* colidx, double* vals);
 int mcx_dump_dirichlet(void* ctx, int64_t* idx, int64_t* n);
 /* y = A x on owned rows (collective when nranks > 1) */
 int mcx_spmv(void* ctx, const double* x_host, double* y_host);
-/* KSP residual history of the last solve (ksp_monitor); *n in: capacity, out: count */
+/* KSP residual history of the last solve (ksp_monitor); *n in: capacity, out: count.  The count is the
+   number of norms that solve computed: the initial one and one per completed iteration, its + 1.  A solve
+   that stops inside an iteration before its norm (MCX_KSP_DIVERGED_INDEFINITE_MAT, _INDEFINITE_PC, z . r
+   == 0) returns its entries: the last one is the norm of iteration its - 1, which mcx_solve's rnorm
+   repeats. */
 int mcx_get_ksp_history(void* ctx, double* hist, int64_t* n);
 
 int mcx_set_timing(void* ctx, int on);

@@ -364,8 +364,16 @@ static int cg_solve(Ctx& c, int* its, double* rnorm, int* reason) {
   *reason = fin.reason;
   c.last_its = fin.its;
   if (c.o.ksp_monitor) {
-    c.last_hist.resize(fin.its + 1);
-    MCX_HIP(hipMemcpy(c.last_hist.data(), c.hist, sizeof(double) * (fin.its + 1), hipMemcpyDeviceToHost));
+    // the norms this solve computed: entry 0 and one per completed iteration.  A stop before the
+    // iteration's norm (INDEFINITE_MAT at the alpha step; z.r == 0 or INDEFINITE_PC at the top of the
+    // next one, where its already counts it) leaves its entries, not its + 1: c.hist beyond them
+    // is an earlier solve's
+    const bool before_norm = fin.reason == MCX_KSP_DIVERGED_INDEFINITE_MAT ||
+                             fin.reason == MCX_KSP_DIVERGED_INDEFINITE_PC ||
+                             (fin.reason == MCX_KSP_CONVERGED_ATOL && fin.beta == 0.);
+    const int nh = before_norm ? std::max(fin.its, 1) : fin.its + 1;
+    c.last_hist.resize(nh);
+    MCX_HIP(hipMemcpy(c.last_hist.data(), c.hist, sizeof(double) * nh, hipMemcpyDeviceToHost));
   }
   if (c.timing) {
     int n = 0;  // pairs around iterations that ran (later launches of the last chunk return at once)
