@@ -425,7 +425,8 @@ int mcx_set_option(void* ctx, const char* name, double value);
    -micro_mem lds|device ("micro_mem" 0 | 1), -micro_solver cell|grid ("micro_solver" 0 | 1),
    -micro_rtol, -micro_max_it, -micro_nl_rtol, -micro_nl_max_it, -micro_nl_slots (each with a
    number), -pc_type jacobi|mg ("pc_type" 0 | 1), -pc_mg_levels N, -mg_levels_ksp_max_it k
-   ("pc_mg_smooth"), -pc_mg_dist 0|1 ("pc_mg_dist"; give it before -pc_type).  mcx_parse_args accepts these flags and checks -micro_mem's and -micro_solver's word; call this after mcx_init with the same argv.  Other flags are skipped. */
+   ("pc_mg_smooth"), -pc_mg_dist 0|1 ("pc_mg_dist"; give it before -pc_type), -pc_mg_precision
+   double|single ("pc_mg_precision" 0 | 1).  mcx_parse_args accepts these flags and checks -micro_mem's, -micro_solver's and -pc_mg_precision's word; call this after mcx_init with the same argv.  Other flags are skipped. */
 int mcx_apply_args(void* ctx, int argc, const char* const* argv);
 int mcx_time_spmv(void* ctx, int iters, double* avg_ms);
 
@@ -455,6 +456,22 @@ int mcx_time_spmv(void* ctx, int iters, double* avg_ms);
  * mcx_solve, mcx_pc_apply, mcx_pc_mg_info and mcx_pc_mg_dump_csr are collective (every rank calls
  * them in the same order), and every rank gets the same iteration count, norms and history.
  * Off by default: the RCCL transport's send/recv has not run between two GPUs yet. */
+/* "pc_mg_precision" (-pc_mg_precision double|single; 0 double, the default, or 1 single; other values
+ * fail with code 1, another word with code 2): with 1 every level >= 1 of the hierarchy, the coarsest
+ * one included, keeps its operator (243 values per node) and its vectors in float, under pc_mg_dist
+ * also the padded residual and the level's halo buffers.  Values are widened as they are loaded, every
+ * expression and every sum is the double hierarchy's, in double, and the result is rounded once, on the
+ * store; level 0 (the assembled matrix, its smoother), the transfers' fine side, the coarsest level's
+ * dense inverse, every dot product and the PCG stay double.  Level 1's operator is the double
+ * hierarchy's rounded to float entry by entry; mcx_pc_mg_dump_csr returns the stored values widened.
+ * M^-1 stays deterministic (the same bits for the same input) and symmetric to float rounding, about
+ * 1e-7 relative, which makes it a slightly variable preconditioner: the PCG took the double
+ * hierarchy's iteration count on every grid measured, at -ksp_rtol 1e-8 and, on 17^3, at 1e-12
+ * (DESIGN §17); a tolerance near the double rounding may cost a few iterations more.  Changing the
+ * value frees a built hierarchy (device_bytes follows); the next use builds it again.  It combines
+ * with pc_mg_levels, pc_mg_smooth, pc_mg_dist, every storage and every law.
+ * mcx_pc_mg_get_precision: the option's value. */
+int mcx_pc_mg_get_precision(void* ctx, int* single);
 /* z = M^-1 r on the owned rows with the current preconditioner (owned rows in, owned rows out) */
 int mcx_pc_apply(void* ctx, const double* r_host, double* z_host);
 /* the hierarchy of pc_type 1 (nlevels 0 otherwise): node counts nxyz[16][3] from the fine level

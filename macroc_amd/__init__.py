@@ -43,6 +43,7 @@ EXPORTS = [
     "mcx_micro_get_ctan", "mcx_micro_get_phase",
     "mcx_get_gp_ctan", "mcx_micro_nl_get_info", "mcx_micro_nl_get_pool", "mcx_apply_args",
     "mcx_pc_apply", "mcx_pc_mg_info", "mcx_pc_mg_dump_csr", "mcx_get_st_dma", "mcx_pc_mg_plan", "mcx_pc_mg_box",
+    "mcx_pc_mg_get_precision",
 ]
 
 LAWS = {"elastic": 0, "plastic": 1, "external": 2, "micro": 3, "micro_nl": 4}
@@ -157,6 +158,7 @@ def lib():
     L.mcx_finalize.argtypes = [vp]
     L.mcx_get_info.argtypes = [vp, C.POINTER(Info)]
     L.mcx_get_st_dma.argtypes = [vp, C.POINTER(C.c_int)]
+    L.mcx_pc_mg_get_precision.argtypes = [vp, C.POINTER(C.c_int)]
     L.mcx_comm_info.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.mcx_material_set.argtypes = [vp, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int]
     L.mcx_get_displacement.argtypes = [vp, C.c_int]
@@ -574,6 +576,12 @@ class Macroc:
         _check(lib().mcx_pc_mg_info(self._ctx, C.byref(nl), _ip(nxyz), _dp(lmax), C.byref(nb)), "mcx_pc_mg_info")
         n = nl.value
         return {"levels": n, "nxyz": nxyz.reshape(16, 3)[:n].copy(), "lmax": lmax[:n].copy(), "bytes": nb.value}
+
+    def pc_mg_precision(self):
+        """the option pc_mg_precision: 0 the whole hierarchy in double, 1 its levels >= 1 stored in float."""
+        single = C.c_int(0)
+        _check(lib().mcx_pc_mg_get_precision(self._ctx, C.byref(single)), "mcx_pc_mg_get_precision")
+        return single.value
 
     def pc_mg_box(self, level):
         """(start [3], count [3]): the box of level `level` this rank owns, global indices."""

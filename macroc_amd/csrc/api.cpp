@@ -400,7 +400,7 @@ using namespace mcx;
 static const char* const kApplyFlags[] = {"-micro_mem",     "-micro_rtol",      "-micro_max_it",  "-micro_nl_rtol",
                                           "-micro_nl_max_it", "-micro_nl_slots", "-micro_solver",
                                           "-pc_type",       "-pc_mg_levels",    "-mg_levels_ksp_max_it",
-                                          "-pc_mg_dist"};
+                                          "-pc_mg_dist",    "-pc_mg_precision"};
 static bool apply_flag(const char* k) {
   for (const char* f : kApplyFlags)
     if (!std::strcmp(k, f)) return true;
@@ -532,6 +532,10 @@ int mcx_parse_args(mcx_opts* o, int argc, const char* const* argv) try {
       }
       if (!std::strcmp(k, "-micro_solver") && (!v || (std::strcmp(v, "cell") && std::strcmp(v, "grid")))) {
         set_error(std::string("-micro_solver: cell or grid, got ") + (v ? v : "(none)"));
+        return 2;
+      }
+      if (!std::strcmp(k, "-pc_mg_precision") && (!v || (std::strcmp(v, "double") && std::strcmp(v, "single")))) {
+        set_error(std::string("-pc_mg_precision: double or single, got ") + (v ? v : "(none)"));
         return 2;
       }
       if (!std::strcmp(k, "-pc_type") && v && std::strcmp(v, "jacobi") && std::strcmp(v, "mg")) {
@@ -690,6 +694,14 @@ int mcx_get_st_dma(void* ctx, int* on) try {
   GUARD(ctx);
   CTX(ctx);
   if (on) *on = c.st_dma_last;
+  return 0;
+} MCX_CATCH
+
+int mcx_pc_mg_get_precision(void* ctx, int* single) try {
+  MCX_ENTRY();
+  GUARD(ctx);
+  CTX(ctx);
+  if (single) *single = c.pc_mg_precision;
   return 0;
 } MCX_CATCH
 
@@ -1915,7 +1927,7 @@ int mcx_pc_apply(void* ctx, const double* r_host, double* z_host) try {
   if (c.pc_type == 1) {
     int rc = pcmg_apply(c, c.tmp);
     if (rc) return rc;
-    launch_copy_pad_to_owned(c, c.mg.L[0].x, c.tmp);
+    launch_copy_pad_to_owned(c, c.mg.L[0].x.as<double>(), c.tmp);
   } else {
     launch_jacobi(c);
     launch_pcmg_jacobi(c, n3, c.tmp, c.dinv, c.w);
@@ -1967,10 +1979,13 @@ int mcx_pc_mg_dump_csr(void* ctx, int level, int64_t* rowptr, int64_t* colidx, d
   // natural numbering (one rank: the same thing)
   const PcmgLevel& v = c.mg.L[level];
   std::vector<double> blk;
-  if (vals) {
+  if (vals) {  // a float level's values widened (exactly)
     blk.resize((size_t)243 * v.nn);
-    MCX_HIP(hipMemcpyAsync(blk.data(), v.A, sizeof(double) * blk.size(), hipMemcpyDeviceToHost, c.stream));
+    std::vector<float> blk32(v.f32 ? blk.size() : 0);
+    MCX_HIP(hipMemcpyAsync(v.f32 ? (void*)blk32.data() : (void*)blk.data(), v.A.p,
+                           (v.f32 ? sizeof(float) : sizeof(double)) * blk.size(), hipMemcpyDeviceToHost, c.stream));
     MCX_HIP(hipStreamSynchronize(c.stream));
+    for (size_t q = 0; q < blk32.size(); q++) blk[q] = blk32[q];
   }
   int64_t pos = 0;
   if (rowptr) rowptr[0] = 0;
@@ -2195,6 +2210,15 @@ int mcx_set_option(void* ctx, const char* name, double value) try {
       return 2;
     }
     c.pc_mg_dist = (int)value;  // without a communicator it changes nothing
+    return 0;
+  }
+  if (!std::strcmp(name, "pc_mg_precision")) {  // the storage of the hierarchy's levels >= 1
+    if (value != 0. && value != 1.) {
+      set_error("pc_mg_precision: 0 (double: the whole hierarchy in double) or 1 (single: the levels >= 1 stored in float)");
+      return 1;
+    }
+    if ((int)value != c.pc_mg_precision) pcmg_free(c);  // the next use builds the hierarchy in the other type
+    c.pc_mg_precision = (int)value;
     return 0;
   }
   if (!std::strcmp(name, "pc_type")) {  // the macro CG's preconditioner: 0 Jacobi, 1 geometric multigrid
@@ -2647,6 +2671,12 @@ int mcx_apply_args(void* ctx, int argc, const char* const* argv) try {
         return 2;
       }
       value = std::strcmp(v, "grid") ? 0. : 1.;
+    } else if (!std::strcmp(k, "-pc_mg_precision")) {
+      if (std::strcmp(v, "double") && std::strcmp(v, "single")) {
+        set_error(std::string("-pc_mg_precision: double or single, got ") + v);
+        return 2;
+      }
+      value = std::strcmp(v, "single") ? 0. : 1.;
     } else if (!std::strcmp(k, "-pc_type")) {
       if (std::strcmp(v, "jacobi") && std::strcmp(v, "mg")) {
         set_error(std::string("only -ksp_type cg / -pc_type jacobi / mg are implemented, got ") + v);

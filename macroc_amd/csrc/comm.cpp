@@ -208,9 +208,11 @@ int comm_wait(Ctx& c, hipEvent_t ev, const char* what) {
 // exchange being complete on the host side before the next one starts.
 static const HaloPlan& peer_plan(const Ctx& q, const HaloPlan& h) { return h.level < 0 ? q.halo : q.mg.L[h.level].halo; }
 
-int halo_start(Ctx& c, HaloPlan& h, double* xpad) {
+int halo_start(Ctx& c, HaloPlan& h, void* xpad) {
   if (c.nranks <= 1 || h.nbr_rank.empty()) return 0;
   if (int rc = comm_check(c)) return rc;
+  const size_t esz = (size_t)h.esz;  // the bytes of a value: a float level of the multigrid sends floats
+  const ncclDataType_t type = h.esz == 4 ? ncclFloat : ncclDouble;
   if (c.lg) {
     LocalGroup* g = c.lg;
     // neighbours finished reading my previous send buffer
@@ -226,13 +228,14 @@ int halo_start(Ctx& c, HaloPlan& h, double* xpad) {
       const HaloPlan& qh = peer_plan(q, h);
       size_t idx = 0;
       while (idx < qh.nbr_rank.size() && qh.nbr_rank[idx] != c.rank) idx++;
-      if (idx == qh.nbr_rank.size() || qh.send_cnt[idx] != h.recv_cnt[t] || !qh.d_sendbuf) {
+      if (idx == qh.nbr_rank.size() || qh.send_cnt[idx] != h.recv_cnt[t] || !qh.d_sendbuf || qh.esz != h.esz) {
         set_error("local halo: inconsistent neighbour plans");
         return 22;
       }
       MCX_HIP(hipStreamWaitEvent(c.comm_stream, g->ev_packed[h.nbr_rank[t]], 0));
-      MCX_HIP(hipMemcpyAsync(h.d_recvbuf + 3 * h.recv_off[t], qh.d_sendbuf + 3 * qh.send_off[idx],
-                             sizeof(double) * 3 * h.recv_cnt[t], hipMemcpyDeviceToDevice, c.comm_stream));
+      MCX_HIP(hipMemcpyAsync(static_cast<char*>(h.d_recvbuf) + esz * 3 * h.recv_off[t],
+                             static_cast<const char*>(qh.d_sendbuf) + esz * 3 * qh.send_off[idx], esz * 3 * h.recv_cnt[t],
+                             hipMemcpyDeviceToDevice, c.comm_stream));
     }
     MCX_HIP(hipEventRecord(g->ev_halo_done[c.rank], c.comm_stream));
     MCX_HIP(hipEventRecord(c.ev_comm, c.comm_stream));
@@ -245,9 +248,9 @@ int halo_start(Ctx& c, HaloPlan& h, double* xpad) {
   MCX_HIP(hipStreamWaitEvent(c.comm_stream, c.ev_pack, 0));
   MCX_NCCL(ncclGroupStart());
   for (size_t q = 0; q < h.nbr_rank.size(); q++) {
-    MCX_NCCL(ncclSend(h.d_sendbuf + 3 * h.send_off[q], 3 * h.send_cnt[q], ncclDouble, h.nbr_rank[q],
-                      (ncclComm_t)c.comm, c.comm_stream));
-    MCX_NCCL(ncclRecv(h.d_recvbuf + 3 * h.recv_off[q], 3 * h.recv_cnt[q], ncclDouble, h.nbr_rank[q],
+    MCX_NCCL(ncclSend(static_cast<const char*>(h.d_sendbuf) + esz * 3 * h.send_off[q], 3 * h.send_cnt[q], type,
+                      h.nbr_rank[q], (ncclComm_t)c.comm, c.comm_stream));
+    MCX_NCCL(ncclRecv(static_cast<char*>(h.d_recvbuf) + esz * 3 * h.recv_off[q], 3 * h.recv_cnt[q], type, h.nbr_rank[q],
                       (ncclComm_t)c.comm, c.comm_stream));
   }
   MCX_NCCL(ncclGroupEnd());
@@ -255,14 +258,14 @@ int halo_start(Ctx& c, HaloPlan& h, double* xpad) {
   return 0;
 }
 
-int halo_finish(Ctx& c, HaloPlan& h, double* xpad) {
+int halo_finish(Ctx& c, HaloPlan& h, void* xpad) {
   if (c.nranks <= 1 || h.nbr_rank.empty()) return 0;
   MCX_HIP(hipStreamWaitEvent(c.stream, c.ev_comm, 0));
   launch_unpack(c, h, xpad);
   return 0;
 }
 
-int halo_exchange(Ctx& c, HaloPlan& h, double* xpad) {
+int halo_exchange(Ctx& c, HaloPlan& h, void* xpad) {
   int rc = halo_start(c, h, xpad);
   return rc ? rc : halo_finish(c, h, xpad);
 }

@@ -242,11 +242,11 @@ int build_halo_plan(Ctx& c, HaloPlan& h, const int n3[3], int PX, int PXY, int64
   if (h.nsend == 0) return 0;
   MCX_HIP(hipMalloc(&h.d_send_idx, sizeof(int) * h.nsend));
   MCX_HIP(hipMalloc(&h.d_recv_idx, sizeof(int) * h.nrecv));
-  MCX_HIP(hipMalloc(&h.d_sendbuf, sizeof(double) * 3 * h.nsend));
-  MCX_HIP(hipMalloc(&h.d_recvbuf, sizeof(double) * 3 * h.nrecv));
+  MCX_HIP(hipMalloc(&h.d_sendbuf, (size_t)h.esz * 3 * h.nsend));
+  MCX_HIP(hipMalloc(&h.d_recvbuf, (size_t)h.esz * 3 * h.nrecv));
   MCX_HIP(hipMemcpy(h.d_send_idx, sidx.data(), sizeof(int) * h.nsend, hipMemcpyHostToDevice));
   MCX_HIP(hipMemcpy(h.d_recv_idx, ridx.data(), sizeof(int) * h.nrecv, hipMemcpyHostToDevice));
-  *bytes += (int64_t)(sizeof(int) + 3 * sizeof(double)) * (h.nsend + h.nrecv);
+  *bytes += (int64_t)(sizeof(int) + 3 * h.esz) * (h.nsend + h.nrecv);
   // the sent nodes once each, as owned indices (their p update runs before the exchange)
   const int PY = PXY / PX;
   std::vector<int> bnd(sidx);

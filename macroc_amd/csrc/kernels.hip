@@ -6741,17 +6741,18 @@ __global__ void k_unpack(const int* __restrict__ idx, int64_t cnt, const double*
   for (int d = 0; d < 3; d++) pad[3 * (int64_t)p + d] = buf[3 * t + d];
 }
 
-// a multigrid level's box (pc_mg_dist): one thread per (node, component), cnt3 = 3 x nodes
-__global__ void k_pcmg_pack(const int* __restrict__ idx, int64_t cnt3, const double* __restrict__ pad,
-                            double* __restrict__ buf) {
+// a multigrid level's box (pc_mg_dist): one thread per (node, component), cnt3 = 3 x nodes; T: the
+// level's storage type (float under pc_mg_precision 1)
+template <class T>
+__global__ void k_pcmg_pack(const int* __restrict__ idx, int64_t cnt3, const T* __restrict__ pad, T* __restrict__ buf) {
   const int64_t t = (int64_t)blockIdx.x * TPB + threadIdx.x;
   if (t >= cnt3) return;
   const int64_t q = t / 3;
   buf[t] = pad[3 * (int64_t)idx[q] + (t - 3 * q)];
 }
 
-__global__ void k_pcmg_unpack(const int* __restrict__ idx, int64_t cnt3, const double* __restrict__ buf,
-                              double* __restrict__ pad) {
+template <class T>
+__global__ void k_pcmg_unpack(const int* __restrict__ idx, int64_t cnt3, const T* __restrict__ buf, T* __restrict__ pad) {
   const int64_t t = (int64_t)blockIdx.x * TPB + threadIdx.x;
   if (t >= cnt3) return;
   const int64_t q = t / 3;
@@ -8168,22 +8169,30 @@ void launch_copy_pad_to_owned(Ctx& c, const double* pad, double* owned) {
 
 // the context's plan: one thread per node (k_pack / k_unpack); a multigrid level's box (h.level >= 1):
 // one thread per (node, component)
-void launch_pack(Ctx& c, const HaloPlan& h, const double* xpad) {
+void launch_pack(Ctx& c, const HaloPlan& h, const void* xpad) {
   if (!h.nsend) return;
   if (h.level < 0)
-    hipLaunchKernelGGL(k_pack, dim3(nblk(h.nsend)), dim3(TPB), 0, c.stream, h.d_send_idx, h.nsend, xpad, h.d_sendbuf);
+    hipLaunchKernelGGL(k_pack, dim3(nblk(h.nsend)), dim3(TPB), 0, c.stream, h.d_send_idx, h.nsend,
+                       static_cast<const double*>(xpad), static_cast<double*>(h.d_sendbuf));
+  else if (h.esz == 4)
+    hipLaunchKernelGGL(k_pcmg_pack<float>, dim3(nblk(3 * h.nsend)), dim3(TPB), 0, c.stream, h.d_send_idx, 3 * h.nsend,
+                       static_cast<const float*>(xpad), static_cast<float*>(h.d_sendbuf));
   else
-    hipLaunchKernelGGL(k_pcmg_pack, dim3(nblk(3 * h.nsend)), dim3(TPB), 0, c.stream, h.d_send_idx, 3 * h.nsend, xpad,
-                       h.d_sendbuf);
+    hipLaunchKernelGGL(k_pcmg_pack<double>, dim3(nblk(3 * h.nsend)), dim3(TPB), 0, c.stream, h.d_send_idx, 3 * h.nsend,
+                       static_cast<const double*>(xpad), static_cast<double*>(h.d_sendbuf));
 }
 
-void launch_unpack(Ctx& c, const HaloPlan& h, double* xpad) {
+void launch_unpack(Ctx& c, const HaloPlan& h, void* xpad) {
   if (!h.nrecv) return;
   if (h.level < 0)
-    hipLaunchKernelGGL(k_unpack, dim3(nblk(h.nrecv)), dim3(TPB), 0, c.stream, h.d_recv_idx, h.nrecv, h.d_recvbuf, xpad);
+    hipLaunchKernelGGL(k_unpack, dim3(nblk(h.nrecv)), dim3(TPB), 0, c.stream, h.d_recv_idx, h.nrecv,
+                       static_cast<const double*>(h.d_recvbuf), static_cast<double*>(xpad));
+  else if (h.esz == 4)
+    hipLaunchKernelGGL(k_pcmg_unpack<float>, dim3(nblk(3 * h.nrecv)), dim3(TPB), 0, c.stream, h.d_recv_idx, 3 * h.nrecv,
+                       static_cast<const float*>(h.d_recvbuf), static_cast<float*>(xpad));
   else
-    hipLaunchKernelGGL(k_pcmg_unpack, dim3(nblk(3 * h.nrecv)), dim3(TPB), 0, c.stream, h.d_recv_idx, 3 * h.nrecv,
-                       h.d_recvbuf, xpad);
+    hipLaunchKernelGGL(k_pcmg_unpack<double>, dim3(nblk(3 * h.nrecv)), dim3(TPB), 0, c.stream, h.d_recv_idx,
+                       3 * h.nrecv, static_cast<const double*>(h.d_recvbuf), static_cast<double*>(xpad));
 }
 
 // reduce partials into out (and, for RED_NORM, out[0] = sqrt); multi-rank: local sums are
@@ -8479,6 +8488,10 @@ int cg_iteration(Ctx& c, hipEvent_t ev0, hipEvent_t ev1, bool first, bool last) 
 // ============================================================================ -pc_type mg
 // Geometric multigrid preconditioner (pcmg.cpp).  All of these are streams: one thread
 // per node, consecutive threads on consecutive nodes, every sum in a fixed order.
+// Every kernel that touches a level >= 1 is a template on that level's storage type T (TF / TC: of
+// the finer / the coarser level of a transfer): double, or float under pc_mg_precision 1 (DESIGN
+// §17).  A value is widened to double as it is loaded, the expressions are the double kernel's, and
+// the result is narrowed once, on the store; T = double is the hierarchy without the option.
 __device__ __forceinline__ int64_t pcmg_at(const PcmgLay& l, int i, int j, int k) {
   return (i + l.off) + (int64_t)(j + l.off) * l.PX + (int64_t)(k + l.off) * l.PXY;
 }
@@ -8521,10 +8534,11 @@ __global__ void k_pcmg_mask0(Geo g, unsigned char* __restrict__ mask) {
   mask[n] = (unsigned char)dirichlet_mask(g, g.xs + i, g.ys + j, g.zs + k);
 }
 
-__global__ __launch_bounds__(TPB) void k_pcmg_prolong(PcmgXfer t, PcmgLay lx, PcmgLay lc, const double* __restrict__ xc,
+template <class TF, class TC>
+__global__ __launch_bounds__(TPB) void k_pcmg_prolong(PcmgXfer t, PcmgLay lx, PcmgLay lc, const TC* __restrict__ xc,
                                                       int probe,
                                                       const unsigned char* __restrict__ fmask,
-                                                      double* __restrict__ xf, int add) {
+                                                      TF* __restrict__ xf, int add) {
   const int64_t nf = (int64_t)t.fn[0] * t.fn[1] * t.fn[2];
   const int64_t n = (int64_t)blockIdx.x * TPB + threadIdx.x;
   if (n >= nf) return;
@@ -8546,7 +8560,7 @@ __global__ __launch_bounds__(TPB) void k_pcmg_prolong(PcmgXfer t, PcmgLay lx, Pc
         } else {
           const int64_t q = 3 * pcmg_at(lc, I - t.cs[0], J - t.cs[1], K - t.cs[2]);
 #pragma unroll
-          for (int d = 0; d < 3; d++) v[d] += wt * xc[q + d];
+          for (int d = 0; d < 3; d++) v[d] += wt * (double)xc[q + d];
         }
       }
   const int m = fmask[n];
@@ -8554,14 +8568,15 @@ __global__ __launch_bounds__(TPB) void k_pcmg_prolong(PcmgXfer t, PcmgLay lx, Pc
 #pragma unroll
   for (int d = 0; d < 3; d++) {
     const double vd = (m >> d & 1) ? 0. : v[d];
-    xf[q + d] = add ? xf[q + d] + vd : vd;
+    xf[q + d] = (TF)(add ? (double)xf[q + d] + vd : vd);
   }
 }
 
-__global__ __launch_bounds__(TPB) void k_pcmg_restrict(PcmgXfer t, PcmgLay lb, const double* __restrict__ b,
-                                                       const double* __restrict__ w,
+template <class TF, class TC>
+__global__ __launch_bounds__(TPB) void k_pcmg_restrict(PcmgXfer t, PcmgLay lb, const TF* __restrict__ b,
+                                                       const TF* __restrict__ w,
                                                        const unsigned char* __restrict__ fmask,
-                                                       double* __restrict__ bc) {
+                                                       TC* __restrict__ bc) {
   const int64_t ncn = (int64_t)t.cn[0] * t.cn[1] * t.cn[2];
   const int64_t n = (int64_t)blockIdx.x * TPB + threadIdx.x;
   if (n >= ncn) return;
@@ -8585,18 +8600,21 @@ __global__ __launch_bounds__(TPB) void k_pcmg_restrict(PcmgXfer t, PcmgLay lb, c
         const int m = fmask ? fmask[f] : 0;
 #pragma unroll
         for (int d = 0; d < 3; d++) {
-          const double rv = w ? b[fb + d] - w[3 * f + d] : b[fb + d];
+          const double rv = w ? (double)b[fb + d] - (double)w[3 * f + d] : (double)b[fb + d];
           if (!(m >> d & 1)) acc[d] += wt * rv;
         }
       }
 #pragma unroll
-  for (int d = 0; d < 3; d++) bc[3 * n + d] = acc[d];
+  for (int d = 0; d < 3; d++) bc[3 * n + d] = (TC)acc[d];
 }
 
-// r = b - A x (b null: r = A x) with A the level's 27 stencil blocks, slot-major
-__global__ __launch_bounds__(TPB) void k_pcmg_spmv(PcmgLay lx, const double* __restrict__ A,
-                                                   const double* __restrict__ x, const double* __restrict__ b,
-                                                   double* __restrict__ r) {
+// r = b - A x (b null: r = A x) with A the level's 27 stencil blocks, slot-major.  One thread per node
+// on a float level too: a wave's 64 consecutive 4-byte loads are one 256-byte run, and the kernel moves
+// the operator at 0.9 of the double kernel's rate, so in 0.56 of its time (which also lists
+// what 8- and 16-byte loads per thread measured: none was faster)
+template <class T>
+__global__ __launch_bounds__(TPB) void k_pcmg_spmv(PcmgLay lx, const T* __restrict__ A, const T* __restrict__ x,
+                                                   const T* __restrict__ b, T* __restrict__ r) {
   const int nx = lx.nx, ny = lx.ny, nz = lx.nz;
   const int64_t nn = (int64_t)nx * ny * nz;
   const int64_t n = (int64_t)blockIdx.x * TPB + threadIdx.x;
@@ -8611,22 +8629,23 @@ __global__ __launch_bounds__(TPB) void k_pcmg_spmv(PcmgLay lx, const double* __r
       continue;
     const int64_t m = 3 * pcmg_at(lx, ii, jj, kk);
     const double x0 = x[m], x1 = x[m + 1], x2 = x[m + 2];
-    const double* a = A + (int64_t)(nb * 9) * nn + n;
+    const T* a = A + (int64_t)(nb * 9) * nn + n;
 #pragma unroll
     for (int rr = 0; rr < 3; rr++) {
-      acc[rr] = fma(a[(int64_t)(rr * 3) * nn], x0, acc[rr]);
-      acc[rr] = fma(a[(int64_t)(rr * 3 + 1) * nn], x1, acc[rr]);
-      acc[rr] = fma(a[(int64_t)(rr * 3 + 2) * nn], x2, acc[rr]);
+      acc[rr] = fma((double)a[(int64_t)(rr * 3) * nn], x0, acc[rr]);
+      acc[rr] = fma((double)a[(int64_t)(rr * 3 + 1) * nn], x1, acc[rr]);
+      acc[rr] = fma((double)a[(int64_t)(rr * 3 + 2) * nn], x2, acc[rr]);
     }
   }
 #pragma unroll
-  for (int d = 0; d < 3; d++) r[3 * n + d] = b ? b[3 * n + d] - acc[d] : acc[d];
+  for (int d = 0; d < 3; d++) r[3 * n + d] = (T)(b ? (double)b[3 * n + d] - acc[d] : acc[d]);
 }
 
 // Galerkin probe: t = P^T A P e with e the indicator of colour (a, b, c) = (I, J, K) mod 3 and
 // component d.  Node J has at most one neighbour of that colour: t[J] is column d of the block
 // toward it.
-__global__ void k_pcmg_scatter(PcmgLay lx, const double* __restrict__ t, double* __restrict__ A, int colour, int d) {
+template <class T>
+__global__ void k_pcmg_scatter(PcmgLay lx, const T* __restrict__ t, T* __restrict__ A, int colour, int d) {
   const int nx = lx.nx, ny = lx.ny, nz = lx.nz;
   const int64_t nn = (int64_t)nx * ny * nz;
   const int64_t n = (int64_t)blockIdx.x * TPB + threadIdx.x;
@@ -8646,29 +8665,32 @@ __global__ void k_pcmg_scatter(PcmgLay lx, const double* __restrict__ t, double*
 
 // the level's inverse diagonal; a dof whose Galerkin diagonal is exactly 0 (every fine dof it
 // interpolates to is a Dirichlet dof) gets a unit diagonal and its mask bit
-__global__ void k_pcmg_diag(int64_t nn, double* __restrict__ A, double* __restrict__ dinv,
+template <class T>
+__global__ void k_pcmg_diag(int64_t nn, T* __restrict__ A, T* __restrict__ dinv,
                             unsigned char* __restrict__ mask) {
   const int64_t n = (int64_t)blockIdx.x * TPB + threadIdx.x;
   if (n >= nn) return;
   int m = 0;
 #pragma unroll
   for (int d = 0; d < 3; d++) {
-    double* p = A + (int64_t)(13 * 9 + d * 4) * nn + n;
+    T* p = A + (int64_t)(13 * 9 + d * 4) * nn + n;
     double a = *p;
     if (a == 0.) {
-      *p = a = 1.;
+      a = 1.;
+      *p = (T)1.;
       m |= 1 << d;
     }
-    dinv[3 * n + d] = 1. / a;
+    dinv[3 * n + d] = (T)(1. / a);
   }
   mask[n] = (unsigned char)m;
 }
 
 // one Chebyshev step: r = b - w (w null: r = b), d = ca d + cb D^-1 r (dfirst: the first term is
 // dropped), x += d (xzero: x = d)
-__global__ void k_pcmg_cheb(PcmgLay lx, int64_t nn, const double* __restrict__ b, const double* __restrict__ w,
-                            const double* __restrict__ dinv, double* __restrict__ dv, double* __restrict__ x, double ca,
-                            double cb, int dfirst, int xzero) {
+template <class T>
+__global__ void k_pcmg_cheb(PcmgLay lx, int64_t nn, const T* __restrict__ b, const T* __restrict__ w,
+                            const T* __restrict__ dinv, T* __restrict__ dv, T* __restrict__ x, double ca, double cb,
+                            int dfirst, int xzero) {
   const int64_t n = (int64_t)blockIdx.x * TPB + threadIdx.x;
   if (n >= nn) return;
   const int nq = (int)n, i = nq % lx.nx, j = (nq / lx.nx) % lx.ny, k = nq / (lx.nx * lx.ny);  // 32-bit divisions
@@ -8676,28 +8698,30 @@ __global__ void k_pcmg_cheb(PcmgLay lx, int64_t nn, const double* __restrict__ b
 #pragma unroll
   for (int d = 0; d < 3; d++) {
     const int64_t q = 3 * n + d;
-    const double rv = w ? b[q] - w[q] : b[q];
-    const double z = cb * (dinv[q] * rv);
-    const double dn = dfirst ? z : ca * dv[q] + z;
-    dv[q] = dn;
-    x[xq + d] = xzero ? dn : x[xq + d] + dn;
+    const double rv = w ? (double)b[q] - (double)w[q] : (double)b[q];
+    const double z = cb * ((double)dinv[q] * rv);
+    const double dn = dfirst ? z : ca * (double)dv[q] + z;
+    dv[q] = (T)dn;
+    x[xq + d] = (T)(xzero ? dn : (double)x[xq + d] + dn);
   }
 }
 
-// x = Ainv b, one wave per row
-__global__ __launch_bounds__(TPB) void k_pcmg_gemv(int n, const double* __restrict__ ainv, const double* __restrict__ b,
-                                                   double* __restrict__ x) {
+// x = Ainv b, one wave per row (Ainv is double always)
+template <class T>
+__global__ __launch_bounds__(TPB) void k_pcmg_gemv(int n, const double* __restrict__ ainv, const T* __restrict__ b,
+                                                   T* __restrict__ x) {
   const int row = blockIdx.x * (TPB / 64) + (threadIdx.x >> 6), l = threadIdx.x & 63;
   if (row >= n) return;
   const double* a = ainv + (int64_t)row * n;
   double s = 0.;
-  for (int q = l; q < n; q += 64) s = fma(a[q], b[q], s);
+  for (int q = l; q < n; q += 64) s = fma(a[q], (double)b[q], s);
   s = wave_sum(s);
-  if (l == 0) x[row] = s;
+  if (l == 0) x[row] = (T)s;
 }
 
 // the power iteration's start vector: the same pseudo-random values in (-1/2, 1/2) every time
-__global__ void k_pcmg_seed(PcmgLay lx, int64_t nn, double* __restrict__ x) {
+template <class T>
+__global__ void k_pcmg_seed(PcmgLay lx, int64_t nn, T* __restrict__ x) {
   const int64_t n = (int64_t)blockIdx.x * TPB + threadIdx.x;
   if (n >= nn) return;
   const int nq = (int)n, i = nq % lx.nx, j = (nq / lx.nx) % lx.ny, k = nq / (lx.nx * lx.ny);  // 32-bit divisions
@@ -8710,13 +8734,14 @@ __global__ void k_pcmg_seed(PcmgLay lx, int64_t nn, double* __restrict__ x) {
     h ^= h >> 15;
     h *= 2246822519u;
     h ^= h >> 13;
-    x[xq + d] = (double)(h & 0xffffffu) * (1. / 16777216.) - .5 + 1. / 33554432.;
+    x[xq + d] = (T)((double)(h & 0xffffffu) * (1. / 16777216.) - .5 + 1. / 33554432.);
   }
 }
 
-// y = dinv w and the partial sums of y.y
-__global__ __launch_bounds__(TPB) void k_pcmg_scale_dot(int64_t nn, const double* __restrict__ dinv,
-                                                        const double* __restrict__ w, double* __restrict__ y,
+// y = dinv w and the partial sums of y.y (of the products in double, before y is narrowed)
+template <class T>
+__global__ __launch_bounds__(TPB) void k_pcmg_scale_dot(int64_t nn, const T* __restrict__ dinv,
+                                                        const T* __restrict__ w, T* __restrict__ y,
                                                         double* __restrict__ part) {
   __shared__ double sh[TPB / 64];
   const int64_t n = (int64_t)blockIdx.x * TPB + threadIdx.x;
@@ -8724,8 +8749,8 @@ __global__ __launch_bounds__(TPB) void k_pcmg_scale_dot(int64_t nn, const double
   if (n < nn) {
 #pragma unroll
     for (int d = 0; d < 3; d++) {
-      const double v = dinv[3 * n + d] * w[3 * n + d];
-      y[3 * n + d] = v;
+      const double v = (double)dinv[3 * n + d] * (double)w[3 * n + d];
+      y[3 * n + d] = (T)v;
       s += v * v;
     }
   }
@@ -8733,13 +8758,14 @@ __global__ __launch_bounds__(TPB) void k_pcmg_scale_dot(int64_t nn, const double
   if (threadIdx.x == 0) part[blockIdx.x] = s;
 }
 
-__global__ void k_pcmg_scaleto(PcmgLay lx, int64_t nn, const double* __restrict__ y, double s, double* __restrict__ x) {
+template <class T>
+__global__ void k_pcmg_scaleto(PcmgLay lx, int64_t nn, const T* __restrict__ y, double s, T* __restrict__ x) {
   const int64_t n = (int64_t)blockIdx.x * TPB + threadIdx.x;
   if (n >= nn) return;
   const int nq = (int)n, i = nq % lx.nx, j = (nq / lx.nx) % lx.ny, k = nq / (lx.nx * lx.ny);  // 32-bit divisions
   const int64_t xq = 3 * pcmg_at(lx, i, j, k);
 #pragma unroll
-  for (int d = 0; d < 3; d++) x[xq + d] = s * y[3 * n + d];
+  for (int d = 0; d < 3; d++) x[xq + d] = (T)(s * (double)y[3 * n + d]);
 }
 
 // partial sums of a . b with a in layout la and b in owned order
@@ -8787,8 +8813,9 @@ __global__ void k_pcmg_jacobi(int64_t n, const double* __restrict__ r, const dou
 }
 
 // pc_mg_dist: the masked residual in the padded box (its owner masks, then the ghosts are exchanged)
-__global__ void k_pcmg_resid(PcmgLay lx, int64_t nn, const double* __restrict__ b, const double* __restrict__ w,
-                             const unsigned char* __restrict__ mask, double* __restrict__ rp) {
+template <class T>
+__global__ void k_pcmg_resid(PcmgLay lx, int64_t nn, const T* __restrict__ b, const T* __restrict__ w,
+                             const unsigned char* __restrict__ mask, T* __restrict__ rp) {
   const int64_t n = (int64_t)blockIdx.x * TPB + threadIdx.x;
   if (n >= nn) return;
   const int nq = (int)n, i = nq % lx.nx, j = (nq / lx.nx) % lx.ny, k = nq / (lx.nx * lx.ny);  // 32-bit divisions
@@ -8796,13 +8823,14 @@ __global__ void k_pcmg_resid(PcmgLay lx, int64_t nn, const double* __restrict__ 
   const int m = mask[n];
 #pragma unroll
   for (int d = 0; d < 3; d++) {
-    const double rv = w ? b[3 * n + d] - w[3 * n + d] : b[3 * n + d];
-    rp[xq + d] = (m >> d & 1) ? 0. : rv;
+    const double rv = w ? (double)b[3 * n + d] - (double)w[3 * n + d] : (double)b[3 * n + d];
+    rp[xq + d] = (T)((m >> d & 1) ? 0. : rv);
   }
 }
 
 // pc_mg_dist, the coarsest level: the rank's owned entries of the level's global vector (natural order)
-__global__ void k_pcmg_to_full(PcmgLay lx, int64_t nn, const double* __restrict__ v, double* __restrict__ full) {
+template <class T>
+__global__ void k_pcmg_to_full(PcmgLay lx, int64_t nn, const T* __restrict__ v, double* __restrict__ full) {
   const int64_t n = (int64_t)blockIdx.x * TPB + threadIdx.x;
   if (n >= nn) return;
   const int nq = (int)n, i = nq % lx.nx, j = (nq / lx.nx) % lx.ny, k = nq / (lx.nx * lx.ny);  // 32-bit divisions
@@ -8812,7 +8840,8 @@ __global__ void k_pcmg_to_full(PcmgLay lx, int64_t nn, const double* __restrict_
 }
 
 // ... and back: the rank's padded box of the global vector, ghosts included, 0 outside the grid
-__global__ void k_pcmg_from_full(PcmgLay lx, const double* __restrict__ full, double* __restrict__ xpad) {
+template <class T>
+__global__ void k_pcmg_from_full(PcmgLay lx, const double* __restrict__ full, T* __restrict__ xpad) {
   const int bx = lx.nx + 2, by = lx.ny + 2, bz = lx.nz + 2;
   const int n = blockIdx.x * TPB + threadIdx.x;
   if (n >= bx * by * bz) return;
@@ -8821,11 +8850,12 @@ __global__ void k_pcmg_from_full(PcmgLay lx, const double* __restrict__ full, do
   const bool in = gi >= 0 && gj >= 0 && gk >= 0 && gi < lx.gn[0] && gj < lx.gn[1] && gk < lx.gn[2];
   const int64_t gq = gi + (int64_t)lx.gn[0] * (gj + (int64_t)lx.gn[1] * gk), xq = 3 * pcmg_at(lx, i, j, k);
 #pragma unroll
-  for (int d = 0; d < 3; d++) xpad[xq + d] = in ? full[3 * gq + d] : 0.;
+  for (int d = 0; d < 3; d++) xpad[xq + d] = (T)(in ? full[3 * gq + d] : 0.);
 }
 
 // ... and the rank's operator blocks into the global slot-major array [243][NN]: one thread per (slot, node)
-__global__ void k_pcmg_blocks_to_full(PcmgLay lx, int64_t nn, const double* __restrict__ A, int64_t NN,
+template <class T>
+__global__ void k_pcmg_blocks_to_full(PcmgLay lx, int64_t nn, const T* __restrict__ A, int64_t NN,
                                       double* __restrict__ full) {
   const int64_t t = (int64_t)blockIdx.x * TPB + threadIdx.x;
   if (t >= 243 * nn) return;
@@ -8845,54 +8875,114 @@ PcmgLay pcmg_lay_box(const PcmgLevel& v) {
   return PcmgLay{v.n[0], v.n[1], v.n[2], v.n[0] + 2, (v.n[0] + 2) * (v.n[1] + 2), 1, {v.s[0], v.s[1], v.s[2]},
                  {v.N[0], v.N[1], v.N[2]}};
 }
-void launch_pcmg_resid(Ctx& c, const PcmgLay& lx, int64_t nn, const double* b, const double* w, const unsigned char* mask,
-                       double* rp) {
-  hipLaunchKernelGGL(k_pcmg_resid, dim3(nblk(nn)), dim3(TPB), 0, c.stream, lx, nn, b, w, mask, rp);
+// the launch under a level's storage type: f gets a value of that type (float or double) as its tag
+template <class F>
+static void mg_as(bool f32, F&& f) {
+  if (f32) f(float());
+  else f(double());
 }
-void launch_pcmg_to_full(Ctx& c, const PcmgLay& lx, int64_t nn, const double* v, double* full) {
-  hipLaunchKernelGGL(k_pcmg_to_full, dim3(nblk(nn)), dim3(TPB), 0, c.stream, lx, nn, v, full);
+// ... of a transfer between a level (ff: float) and the next coarser one (cf): a float level has no
+// double level below it
+template <class F>
+static void mg_as2(bool ff, bool cf, F&& f) {
+  if (ff && !cf) throw std::logic_error("multigrid: a double level below a float one");
+  if (ff) f(float(), float());
+  else if (cf) f(double(), float());
+  else f(double(), double());
 }
-void launch_pcmg_from_full(Ctx& c, const PcmgLay& lx, const double* full, double* xpad) {
+
+void launch_pcmg_resid(Ctx& c, const PcmgLay& lx, int64_t nn, PcmgVec b, PcmgVec w, const unsigned char* mask,
+                       PcmgVec rp) {
+  mg_as(rp.f32, [&](auto tag) {
+    using T = decltype(tag);
+    hipLaunchKernelGGL(k_pcmg_resid<T>, dim3(nblk(nn)), dim3(TPB), 0, c.stream, lx, nn, b.as<T>(), w.as<T>(), mask,
+                       rp.as<T>());
+  });
+}
+void launch_pcmg_to_full(Ctx& c, const PcmgLay& lx, int64_t nn, PcmgVec v, double* full) {
+  mg_as(v.f32, [&](auto tag) {
+    using T = decltype(tag);
+    hipLaunchKernelGGL(k_pcmg_to_full<T>, dim3(nblk(nn)), dim3(TPB), 0, c.stream, lx, nn, v.as<T>(), full);
+  });
+}
+void launch_pcmg_from_full(Ctx& c, const PcmgLay& lx, const double* full, PcmgVec xpad) {
   const int64_t nb = (int64_t)(lx.nx + 2) * (lx.ny + 2) * (lx.nz + 2);
-  hipLaunchKernelGGL(k_pcmg_from_full, dim3(nblk(nb)), dim3(TPB), 0, c.stream, lx, full, xpad);
+  mg_as(xpad.f32, [&](auto tag) {
+    using T = decltype(tag);
+    hipLaunchKernelGGL(k_pcmg_from_full<T>, dim3(nblk(nb)), dim3(TPB), 0, c.stream, lx, full, xpad.as<T>());
+  });
 }
-void launch_pcmg_blocks_to_full(Ctx& c, const PcmgLay& lx, int64_t nn, const double* A, int64_t NN, double* full) {
-  hipLaunchKernelGGL(k_pcmg_blocks_to_full, dim3(nblk(243 * nn)), dim3(TPB), 0, c.stream, lx, nn, A, NN, full);
+void launch_pcmg_blocks_to_full(Ctx& c, const PcmgLevel& l, const PcmgLay& lx, int64_t NN, double* full) {
+  mg_as(l.A.f32, [&](auto tag) {
+    using T = decltype(tag);
+    hipLaunchKernelGGL(k_pcmg_blocks_to_full<T>, dim3(nblk(243 * l.nn)), dim3(TPB), 0, c.stream, lx, l.nn, l.A.as<T>(),
+                       NN, full);
+  });
 }
 
 void launch_pcmg_mask0(Ctx& c, unsigned char* mask) {
   hipLaunchKernelGGL(k_pcmg_mask0, dim3(nblk(c.g.nown)), dim3(TPB), 0, c.stream, c.g, mask);
 }
-void launch_pcmg_prolong(Ctx& c, const PcmgXfer& t, const PcmgLay& lx, const PcmgLay& lc, const double* xc, int probe,
-                         const unsigned char* fmask, double* xf, bool add) {
+void launch_pcmg_prolong(Ctx& c, const PcmgXfer& t, const PcmgLay& lx, const PcmgLay& lc, PcmgVec xc, int probe,
+                         const unsigned char* fmask, PcmgVec xf, bool add) {
   const int64_t nf = (int64_t)t.fn[0] * t.fn[1] * t.fn[2];
-  hipLaunchKernelGGL(k_pcmg_prolong, dim3(nblk(nf)), dim3(TPB), 0, c.stream, t, lx, lc, xc, probe, fmask, xf,
-                     add ? 1 : 0);
+  mg_as2(xf.f32, xc ? xc.f32 : xf.f32, [&](auto tf, auto tc) {  // a probe has no coarse vector
+    using TF = decltype(tf);
+    using TC = decltype(tc);
+    hipLaunchKernelGGL((k_pcmg_prolong<TF, TC>), dim3(nblk(nf)), dim3(TPB), 0, c.stream, t, lx, lc, xc.as<TC>(), probe,
+                       fmask, xf.as<TF>(), add ? 1 : 0);
+  });
 }
-void launch_pcmg_restrict(Ctx& c, const PcmgXfer& t, const PcmgLay& lb, const double* b, const double* w,
-                          const unsigned char* fmask, double* bc) {
+void launch_pcmg_restrict(Ctx& c, const PcmgXfer& t, const PcmgLay& lb, PcmgVec b, PcmgVec w, const unsigned char* fmask,
+                          PcmgVec bc) {
   const int64_t ncn = (int64_t)t.cn[0] * t.cn[1] * t.cn[2];
-  hipLaunchKernelGGL(k_pcmg_restrict, dim3(nblk(ncn)), dim3(TPB), 0, c.stream, t, lb, b, w, fmask, bc);
+  mg_as2(b.f32, bc.f32, [&](auto tf, auto tc) {
+    using TF = decltype(tf);
+    using TC = decltype(tc);
+    hipLaunchKernelGGL((k_pcmg_restrict<TF, TC>), dim3(nblk(ncn)), dim3(TPB), 0, c.stream, t, lb, b.as<TF>(), w.as<TF>(),
+                       fmask, bc.as<TC>());
+  });
 }
-void launch_pcmg_spmv(Ctx& c, const PcmgLevel& l, const PcmgLay& lx, const double* x, const double* b, double* r) {
-  hipLaunchKernelGGL(k_pcmg_spmv, dim3(nblk(l.nn)), dim3(TPB), 0, c.stream, lx, l.A, x, b, r);
+void launch_pcmg_spmv(Ctx& c, const PcmgLevel& l, const PcmgLay& lx, PcmgVec x, PcmgVec b, PcmgVec r) {
+  mg_as(l.A.f32, [&](auto tag) {
+    using T = decltype(tag);
+    hipLaunchKernelGGL(k_pcmg_spmv<T>, dim3(nblk(l.nn)), dim3(TPB), 0, c.stream, lx, l.A.as<T>(), x.as<T>(), b.as<T>(),
+                       r.as<T>());
+  });
 }
-void launch_pcmg_scatter(Ctx& c, const PcmgLevel& l, const PcmgLay& lx, const double* t, int colour, int d) {
-  hipLaunchKernelGGL(k_pcmg_scatter, dim3(nblk(l.nn)), dim3(TPB), 0, c.stream, lx, t, l.A, colour, d);
+void launch_pcmg_scatter(Ctx& c, const PcmgLevel& l, const PcmgLay& lx, PcmgVec t, int colour, int d) {
+  mg_as(l.A.f32, [&](auto tag) {
+    using T = decltype(tag);
+    hipLaunchKernelGGL(k_pcmg_scatter<T>, dim3(nblk(l.nn)), dim3(TPB), 0, c.stream, lx, t.as<T>(), l.A.as<T>(), colour, d);
+  });
 }
 void launch_pcmg_diag(Ctx& c, const PcmgLevel& l) {
-  hipLaunchKernelGGL(k_pcmg_diag, dim3(nblk(l.nn)), dim3(TPB), 0, c.stream, l.nn, l.A, l.dinv, l.mask);
+  mg_as(l.A.f32, [&](auto tag) {
+    using T = decltype(tag);
+    hipLaunchKernelGGL(k_pcmg_diag<T>, dim3(nblk(l.nn)), dim3(TPB), 0, c.stream, l.nn, l.A.as<T>(), l.dinv.as<T>(),
+                       l.mask);
+  });
 }
-void launch_pcmg_cheb(Ctx& c, const PcmgLay& lx, int64_t nn, const double* b, const double* w, const double* dinv,
-                      double* d, double* x, double ca, double cb, bool dfirst, bool xzero) {
-  hipLaunchKernelGGL(k_pcmg_cheb, dim3(nblk(nn)), dim3(TPB), 0, c.stream, lx, nn, b, w, dinv, d, x, ca, cb,
-                     dfirst ? 1 : 0, xzero ? 1 : 0);
+void launch_pcmg_cheb(Ctx& c, const PcmgLay& lx, int64_t nn, PcmgVec b, PcmgVec w, PcmgVec dinv, PcmgVec d, PcmgVec x,
+                      double ca, double cb, bool dfirst, bool xzero) {
+  mg_as(x.f32, [&](auto tag) {
+    using T = decltype(tag);
+    hipLaunchKernelGGL(k_pcmg_cheb<T>, dim3(nblk(nn)), dim3(TPB), 0, c.stream, lx, nn, b.as<T>(), w.as<T>(),
+                       dinv.as<T>(), d.as<T>(), x.as<T>(), ca, cb, dfirst ? 1 : 0, xzero ? 1 : 0);
+  });
 }
-void launch_pcmg_gemv(Ctx& c, int n, const double* ainv, const double* b, double* x) {
-  hipLaunchKernelGGL(k_pcmg_gemv, dim3((n + TPB / 64 - 1) / (TPB / 64)), dim3(TPB), 0, c.stream, n, ainv, b, x);
+void launch_pcmg_gemv(Ctx& c, int n, const double* ainv, PcmgVec b, PcmgVec x) {
+  mg_as(x.f32, [&](auto tag) {
+    using T = decltype(tag);
+    hipLaunchKernelGGL(k_pcmg_gemv<T>, dim3((n + TPB / 64 - 1) / (TPB / 64)), dim3(TPB), 0, c.stream, n, ainv, b.as<T>(),
+                       x.as<T>());
+  });
 }
-void launch_pcmg_seed(Ctx& c, const PcmgLay& lx, int64_t nn, double* x) {
-  hipLaunchKernelGGL(k_pcmg_seed, dim3(nblk(nn)), dim3(TPB), 0, c.stream, lx, nn, x);
+void launch_pcmg_seed(Ctx& c, const PcmgLay& lx, int64_t nn, PcmgVec x) {
+  mg_as(x.f32, [&](auto tag) {
+    using T = decltype(tag);
+    hipLaunchKernelGGL(k_pcmg_seed<T>, dim3(nblk(nn)), dim3(TPB), 0, c.stream, lx, nn, x.as<T>());
+  });
 }
 // the partial sums of one value -> c.red[0] (k_reduce's fixed tree); a context with a communicator:
 // the rank's sum, then the all-reduce in rank order
@@ -8904,12 +8994,19 @@ static int pcmg_reduce(Ctx& c, int nparts) {
                      (int)RED_STORE, c.cg, c.hist, 0, c.cg);
   return multi ? allreduce_sum(c, c.red_loc, c.red, 1) : 0;
 }
-int launch_pcmg_scale_dot(Ctx& c, int64_t nn, const double* dinv, const double* w, double* y) {
-  hipLaunchKernelGGL(k_pcmg_scale_dot, dim3(nblk(nn)), dim3(TPB), 0, c.stream, nn, dinv, w, y, c.partials);
+int launch_pcmg_scale_dot(Ctx& c, int64_t nn, PcmgVec dinv, PcmgVec w, PcmgVec y) {
+  mg_as(y.f32, [&](auto tag) {
+    using T = decltype(tag);
+    hipLaunchKernelGGL(k_pcmg_scale_dot<T>, dim3(nblk(nn)), dim3(TPB), 0, c.stream, nn, dinv.as<T>(), w.as<T>(),
+                       y.as<T>(), c.partials);
+  });
   return pcmg_reduce(c, (int)nblk(nn));
 }
-void launch_pcmg_scaleto(Ctx& c, const PcmgLay& lx, int64_t nn, const double* y, double s, double* x) {
-  hipLaunchKernelGGL(k_pcmg_scaleto, dim3(nblk(nn)), dim3(TPB), 0, c.stream, lx, nn, y, s, x);
+void launch_pcmg_scaleto(Ctx& c, const PcmgLay& lx, int64_t nn, PcmgVec y, double s, PcmgVec x) {
+  mg_as(x.f32, [&](auto tag) {
+    using T = decltype(tag);
+    hipLaunchKernelGGL(k_pcmg_scaleto<T>, dim3(nblk(nn)), dim3(TPB), 0, c.stream, lx, nn, y.as<T>(), s, x.as<T>());
+  });
 }
 int launch_pcmg_dot(Ctx& c, const PcmgLay& la, int64_t nn, const double* a, const double* b) {
   hipLaunchKernelGGL(k_pcmg_dot, dim3(nblk(nn)), dim3(TPB), 0, c.stream, la, nn, a, b, c.partials);

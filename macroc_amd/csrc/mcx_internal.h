@@ -5,7 +5,9 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <stdexcept>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/macroc_amd.h"
@@ -144,12 +146,34 @@ struct HaloPlan {
   std::vector<int64_t> send_off, send_cnt, recv_off, recv_cnt;  // in nodes
   int* d_send_idx = nullptr;          // padded node index of each sent node
   int* d_recv_idx = nullptr;          // padded node index of each received node
-  double* d_sendbuf = nullptr;
-  double* d_recvbuf = nullptr;
+  void* d_sendbuf = nullptr;         // 3 values per node, esz bytes each
+  void* d_recvbuf = nullptr;
+  int esz = 8;                        // 8: double; 4: a float level of the multigrid (pc_mg_precision 1)
   int64_t nsend = 0, nrecv = 0;
   int* d_bnd = nullptr;               // owned node index of every sent node, each once
   int64_t nbnd = 0;
   int level = -1;                     // -1: the context's plan (Ctx::halo); l >= 1: multigrid level l's box (pc_mg_dist)
+};
+
+// A vector or an operator of a multigrid level together with its storage type: double, or float on a
+// level >= 1 under pc_mg_precision 1.  The type travels with the pointer from where it was
+// allocated, and the launchers ask for the typed pointer: using one as the other type is an error
+// (std::logic_error, which every C entry turns into MCX_EXC), never a silent reinterpretation.
+struct PcmgVec {
+  void* p = nullptr;
+  bool f32 = false;
+  PcmgVec() = default;
+  PcmgVec(std::nullptr_t) {}
+  PcmgVec(double* q) : p(q), f32(false) {}
+  PcmgVec(const double* q) : p(const_cast<double*>(q)), f32(false) {}
+  PcmgVec(float* q) : p(q), f32(true) {}
+  explicit operator bool() const { return p != nullptr; }
+  template <class T>
+  T* as() const {  // a null vector has any type
+    if (p && f32 != std::is_same<T, float>::value)
+      throw std::logic_error("multigrid: a level's vector used as the other storage type");
+    return static_cast<T*>(p);
+  }
 };
 
 struct PcmgLevel {
@@ -157,13 +181,17 @@ struct PcmgLevel {
   int64_t nn = 0;              // ... their product
   int s[3] = {0, 0, 0};        // the box's global start
   int N[3] = {0, 0, 0};        // the level's global node counts (one rank: n)
-  double* rp = nullptr;        // pc_mg_dist: the residual masked by its owner, padded box (what P^T reads after a halo)
+  // pc_mg_precision 1: on a level >= 1 the operator and every vector below are float
+  // (f32; each PcmgVec carries it too), loaded and widened, computed in double and narrowed on the
+  // store; level 0 is double always
+  bool f32 = false;
+  PcmgVec rp;                  // pc_mg_dist: the residual masked by its owner, padded box (what P^T reads after a halo)
   void* rp_base = nullptr;     // ... its allocation on level 0 (aligned as x)
   HaloPlan halo;               // pc_mg_dist, level >= 1: the box's ghost fill (level 0 uses Ctx::halo)
-  double* A = nullptr;         // [243][nn] (levels >= 1)
-  double* x = nullptr;         // the cycle's iterate (level 0: padded box, shifted by pad_off from x_base)
+  PcmgVec A;                   // [243][nn] (levels >= 1)
+  PcmgVec x;                   // the cycle's iterate (level 0: padded box, shifted by pad_off from x_base)
   void* x_base = nullptr;
-  double *b = nullptr, *r = nullptr, *d = nullptr, *dinv = nullptr;  // level 0: b = the cycle's argument, r = c.w, d = c.z, dinv = c.dinv
+  PcmgVec b, r, d, dinv;       // level 0: b = the cycle's argument, r = c.w, d = c.z, dinv = c.dinv
   unsigned char* mask = nullptr;  // [nn] bit d: dof d is a Dirichlet dof (level >= 1: its Galerkin diagonal was 0)
   double lmax = 0.;            // estimate of the largest eigenvalue of D^-1 A
 };
@@ -506,6 +534,7 @@ struct Ctx {
   // options pc_type (0 Jacobi, 1 multigrid), pc_mg_levels (0: automatic), pc_mg_smooth (Chebyshev degree)
   int pc_type = 0, pc_mg_levels = 0, pc_mg_smooth = 2;
   int pc_mg_dist = 0;  // option pc_mg_dist: 1 accepts pc_type 1 on a context with a communicator
+  int pc_mg_precision = 0;  // option pc_mg_precision: 1 keeps the levels >= 1 of the hierarchy in float
   Pcmg mg;
 
   // external Gauss-point law (-mat_law external): host MicroPP-shaped callbacks or a device law
@@ -546,9 +575,10 @@ int64_t count_upper_values(const Ctx& c);
 // ---- communication (comm.cpp)
 int comm_init(Ctx& c, const void* id);
 void comm_destroy(Ctx& c);
-int halo_exchange(Ctx& c, HaloPlan& h, double* xpad);   // halo_start + halo_finish
-int halo_start(Ctx& c, HaloPlan& h, double* xpad);      // pack + exchange on the comm stream
-int halo_finish(Ctx& c, HaloPlan& h, double* xpad);     // compute stream waits, unpacks
+// xpad: double, or float for the plan of a float level of the multigrid (h.esz 4)
+int halo_exchange(Ctx& c, HaloPlan& h, void* xpad);   // halo_start + halo_finish
+int halo_start(Ctx& c, HaloPlan& h, void* xpad);      // pack + exchange on the comm stream
+int halo_finish(Ctx& c, HaloPlan& h, void* xpad);     // compute stream waits, unpacks
 // the context's own plan: its padded vectors (u, p, the multigrid's level 0)
 inline int halo_exchange(Ctx& c, double* xpad) { return halo_exchange(c, c.halo, xpad); }
 inline int halo_start(Ctx& c, double* xpad) { return halo_start(c, c.halo, xpad); }
@@ -602,8 +632,8 @@ void launch_reduce(Ctx& c, int nvals, int nparts, double* out);
 void launch_cg_init(Ctx& c);
 int cg_iteration(Ctx& c, hipEvent_t spmv_start, hipEvent_t spmv_stop, bool first, bool last);
 int cg_finish_init(Ctx& c);
-void launch_pack(Ctx& c, const HaloPlan& h, const double* xpad);
-void launch_unpack(Ctx& c, const HaloPlan& h, double* xpad);
+void launch_pack(Ctx& c, const HaloPlan& h, const void* xpad);  // xpad: double, or float for a plan with esz 4
+void launch_unpack(Ctx& c, const HaloPlan& h, void* xpad);
 void launch_copy_owned_to_pad(Ctx& c, const double* owned, double* pad);
 void launch_copy_pad_to_owned(Ctx& c, const double* pad, double* owned);
 int64_t spmv_grid_blocks(const Ctx& c);
@@ -625,32 +655,35 @@ int dirichlet_mask_host(const Geo& g, int gi, int gj, int gk);
 
 // ---- -pc_type mg: kernels (kernels.hip) and the hierarchy, cycle and PCG loop (pcmg.cpp)
 void launch_pcmg_mask0(Ctx& c, unsigned char* mask);
-// xf (layout lx) = or += P xc; probe >= 0: xc is the indicator of colour probe / 3, component probe % 3
+// A level's vectors and operator come as PcmgVec: the launchers start the kernel's instantiation for
+// the storage type they carry.
+// xf (layout lx) = or += P xc; probe >= 0: xc (null) is the indicator of colour probe / 3, component probe % 3
 // xc in layout lc
-void launch_pcmg_prolong(Ctx& c, const PcmgXfer& t, const PcmgLay& lx, const PcmgLay& lc, const double* xc, int probe,
-                         const unsigned char* fmask, double* xf, bool add);
+void launch_pcmg_prolong(Ctx& c, const PcmgXfer& t, const PcmgLay& lx, const PcmgLay& lc, PcmgVec xc, int probe,
+                         const unsigned char* fmask, PcmgVec xf, bool add);
 // bc = P^T (b - w), b in layout lb; w and fmask (owned order) may be null: pc_mg_dist hands over the
 // masked residual in a padded box, ghosts filled
-void launch_pcmg_restrict(Ctx& c, const PcmgXfer& t, const PcmgLay& lb, const double* b, const double* w,
-                          const unsigned char* fmask, double* bc);
+void launch_pcmg_restrict(Ctx& c, const PcmgXfer& t, const PcmgLay& lb, PcmgVec b, PcmgVec w, const unsigned char* fmask,
+                          PcmgVec bc);
 // r = b - A x (b null: A x), x in layout lx
-void launch_pcmg_spmv(Ctx& c, const PcmgLevel& l, const PcmgLay& lx, const double* x, const double* b, double* r);
-void launch_pcmg_scatter(Ctx& c, const PcmgLevel& l, const PcmgLay& lx, const double* t, int colour, int d);
+void launch_pcmg_spmv(Ctx& c, const PcmgLevel& l, const PcmgLay& lx, PcmgVec x, PcmgVec b, PcmgVec r);
+void launch_pcmg_scatter(Ctx& c, const PcmgLevel& l, const PcmgLay& lx, PcmgVec t, int colour, int d);
 // pc_mg_dist: rp (layout lx, padded) = b - w (w null: b) with the level's Dirichlet dofs zeroed by their owner
-void launch_pcmg_resid(Ctx& c, const PcmgLay& lx, int64_t nn, const double* b, const double* w, const unsigned char* mask,
-                       double* rp);
+void launch_pcmg_resid(Ctx& c, const PcmgLay& lx, int64_t nn, PcmgVec b, PcmgVec w, const unsigned char* mask,
+                       PcmgVec rp);
 // pc_mg_dist, the coarsest level: owned vector -> its entries of the level's global vector; the global
-// vector -> the rank's padded box, ghosts included (0 outside the grid); owned operator blocks -> global [243][NN]
-void launch_pcmg_to_full(Ctx& c, const PcmgLay& lx, int64_t nn, const double* v, double* full);
-void launch_pcmg_from_full(Ctx& c, const PcmgLay& lx, const double* full, double* xpad);
-void launch_pcmg_blocks_to_full(Ctx& c, const PcmgLay& lx, int64_t nn, const double* A, int64_t NN, double* full);
+// vector -> the rank's padded box, ghosts included (0 outside the grid); owned operator blocks -> global
+// [243][NN].  The global side is double always
+void launch_pcmg_to_full(Ctx& c, const PcmgLay& lx, int64_t nn, PcmgVec v, double* full);
+void launch_pcmg_from_full(Ctx& c, const PcmgLay& lx, const double* full, PcmgVec xpad);
+void launch_pcmg_blocks_to_full(Ctx& c, const PcmgLevel& l, const PcmgLay& lx, int64_t NN, double* full);
 void launch_pcmg_diag(Ctx& c, const PcmgLevel& l);
-void launch_pcmg_cheb(Ctx& c, const PcmgLay& lx, int64_t nn, const double* b, const double* w, const double* dinv,
-                      double* d, double* x, double ca, double cb, bool dfirst, bool xzero);
-void launch_pcmg_gemv(Ctx& c, int n, const double* ainv, const double* b, double* x);
-void launch_pcmg_seed(Ctx& c, const PcmgLay& lx, int64_t nn, double* x);
-int launch_pcmg_scale_dot(Ctx& c, int64_t nn, const double* dinv, const double* w, double* y);  // y = dinv w, c.red[0] = y.y (all ranks')
-void launch_pcmg_scaleto(Ctx& c, const PcmgLay& lx, int64_t nn, const double* y, double s, double* x);
+void launch_pcmg_cheb(Ctx& c, const PcmgLay& lx, int64_t nn, PcmgVec b, PcmgVec w, PcmgVec dinv, PcmgVec d, PcmgVec x,
+                      double ca, double cb, bool dfirst, bool xzero);
+void launch_pcmg_gemv(Ctx& c, int n, const double* ainv, PcmgVec b, PcmgVec x);  // x = Ainv b; b and x of one type
+void launch_pcmg_seed(Ctx& c, const PcmgLay& lx, int64_t nn, PcmgVec x);
+int launch_pcmg_scale_dot(Ctx& c, int64_t nn, PcmgVec dinv, PcmgVec w, PcmgVec y);  // y = dinv w, c.red[0] = y.y (all ranks')
+void launch_pcmg_scaleto(Ctx& c, const PcmgLay& lx, int64_t nn, PcmgVec y, double s, PcmgVec x);
 int launch_pcmg_dot(Ctx& c, const PcmgLay& la, int64_t nn, const double* a, const double* b);  // c.red[0] = a.b (all ranks')
 void launch_pcmg_aypx(Ctx& c, int64_t n, const double* z, double bc, double* p, bool first);  // p = z + bc p
 void launch_pcmg_xr(Ctx& c, const PcmgLay& lp, int64_t nn, double a, const double* p, const double* w, double* x,

@@ -63,14 +63,14 @@ void pcmg_free(Ctx& c) {
   for (int l = 0; l < PCMG_MAXLEV; l++) {
     PcmgLevel& v = M.L[l];
     if (v.x_base) (void)hipFree(v.x_base);
-    else if (v.x) (void)hipFree(v.x);
+    else if (v.x) (void)hipFree(v.x.p);
     if (v.rp_base) (void)hipFree(v.rp_base);
-    else if (v.rp) (void)hipFree(v.rp);
-    void* own[] = {v.A, v.mask};
+    else if (v.rp) (void)hipFree(v.rp.p);
+    void* own[] = {v.A.p, v.mask};
     for (void* p : own)
       if (p) (void)hipFree(p);
     if (l > 0)
-      for (void* p : {(void*)v.b, (void*)v.r, (void*)v.d, (void*)v.dinv})
+      for (void* p : {v.b.p, v.r.p, v.d.p, v.dinv.p})
         if (p) (void)hipFree(p);
     free_halo_plan(v.halo);
     v = PcmgLevel();
@@ -90,6 +90,16 @@ static int mg_alloc(Ctx& c, T** p, int64_t n) {
   return 0;
 }
 
+// a vector or an operator of a level: n values of the storage type, which the vector carries from here on
+static int mg_alloc_v(Ctx& c, PcmgVec* v, int64_t n, bool f32) {
+  float* p4 = nullptr;
+  double* p8 = nullptr;
+  const int rc = f32 ? mg_alloc(c, &p4, n) : mg_alloc(c, &p8, n);
+  *v = f32 ? PcmgVec(p4) : PcmgVec(p8);
+  return rc;
+}
+static size_t esz(const PcmgLevel& v) { return v.f32 ? sizeof(float) : sizeof(double); }
+
 static int pcmg_alloc(Ctx& c) {
   Pcmg& M = c.mg;
   if (M.alloc) return 0;
@@ -108,6 +118,7 @@ static int pcmg_alloc(Ctx& c) {
       v.N[a] = P.N[l][a];
     }
     v.nn = (int64_t)v.n[0] * v.n[1] * v.n[2];
+    v.f32 = c.pc_mg_precision == 1 && l > 0;
     if ((rc = mg_alloc(c, &v.mask, v.nn))) return rc;
     if (l == 0) {  // the iterate in the padded box (the SpMV's input), aligned as u and p are
       const int64_t npad = (int64_t)c.g.PX * c.g.PY * c.g.PZ * 3;
@@ -126,13 +137,14 @@ static int pcmg_alloc(Ctx& c) {
       launch_pcmg_mask0(c, v.mask);
     } else {
       const int64_t nbox = M.dist ? (int64_t)(v.n[0] + 2) * (v.n[1] + 2) * (v.n[2] + 2) : v.nn;
-      if ((rc = mg_alloc(c, &v.A, 243 * v.nn)) || (rc = mg_alloc(c, &v.x, 3 * nbox)) ||
-          (rc = mg_alloc(c, &v.b, 3 * v.nn)) || (rc = mg_alloc(c, &v.r, 3 * v.nn)) ||
-          (rc = mg_alloc(c, &v.d, 3 * v.nn)) || (rc = mg_alloc(c, &v.dinv, 3 * v.nn)))
+      if ((rc = mg_alloc_v(c, &v.A, 243 * v.nn, v.f32)) || (rc = mg_alloc_v(c, &v.x, 3 * nbox, v.f32)) ||
+          (rc = mg_alloc_v(c, &v.b, 3 * v.nn, v.f32)) || (rc = mg_alloc_v(c, &v.r, 3 * v.nn, v.f32)) ||
+          (rc = mg_alloc_v(c, &v.d, 3 * v.nn, v.f32)) || (rc = mg_alloc_v(c, &v.dinv, 3 * v.nn, v.f32)))
         return rc;
       if (M.dist) {
-        if ((rc = mg_alloc(c, &v.rp, 3 * nbox))) return rc;
+        if ((rc = mg_alloc_v(c, &v.rp, 3 * nbox, v.f32))) return rc;
         v.halo.level = l;
+        v.halo.esz = (int)esz(v);
         int64_t hb = 0;
         rc = build_halo_plan(c, v.halo, v.n, v.n[0] + 2, (v.n[0] + 2) * (v.n[1] + 2), &hb);
         M.bytes += hb;
@@ -195,23 +207,26 @@ static int read_red(Ctx& c, int n, double* out) {
 }
 
 // pc_mg_dist: fill the ghosts of a padded vector of level l
-static int ghosts(Ctx& c, int l, double* xpad) {
+static int ghosts(Ctx& c, int l, PcmgVec xpad) {
   if (!c.mg.dist) return 0;
-  return l == 0 ? halo_exchange(c, c.halo, xpad) : halo_exchange(c, c.mg.L[l].halo, xpad);
+  if (l == 0) return halo_exchange(c, c.halo, xpad.as<double>());
+  HaloPlan& h = c.mg.L[l].halo;  // its buffers have the level's storage type
+  return halo_exchange(c, h, h.esz == 4 ? (void*)xpad.as<float>() : (void*)xpad.as<double>());
 }
 
 // level l's operator on its iterate: r = b - A x (b null: A x) in v.r
-static int apply_level(Ctx& c, int l, const double* b) {
+static int apply_level(Ctx& c, int l, PcmgVec b) {
   PcmgLevel& v = c.mg.L[l];
   if (int rc = ghosts(c, l, v.x)) return rc;
-  if (l == 0) launch_spmv(c, v.x, v.r, false, false);  // v.r = A x; the callers subtract
+  if (l == 0)  // v.r = A x; the callers subtract
+    launch_spmv(c, v.x.as<double>(), v.r.as<double>(), false, false);
   else launch_pcmg_spmv(c, v, lay_of(c, l), v.x, b, v.r);
   return 0;
 }
 
 // L[l + 1].b = P^T (b - w) with level l's Dirichlet dofs masked (w null: P^T b).  pc_mg_dist: the owner
 // masks the residual into the padded box, one exchange fills its ghosts, P^T reads them
-static int restrict_level(Ctx& c, int l, const double* b, const double* w) {
+static int restrict_level(Ctx& c, int l, PcmgVec b, PcmgVec w) {
   Pcmg& M = c.mg;
   PcmgLevel& v = M.L[l];
   const PcmgXfer t = xfer(M, l);
@@ -262,14 +277,19 @@ static int coarse_inverse(Ctx& c) {
     int rc = allreduce_prepare(c);
     if (rc) return rc;
     MCX_HIP(hipMemsetAsync(M.arin, 0, sizeof(double) * 243 * nn, c.stream));
-    launch_pcmg_blocks_to_full(c, lay_own(c, M.nlev - 1), v.nn, v.A, nn, M.arin);
+    launch_pcmg_blocks_to_full(c, v, lay_own(c, M.nlev - 1), nn, M.arin);
     if ((rc = allreduce_sum_mg(c, M.arout, (int)(243 * nn)))) return rc;
     MCX_HIP(hipMemcpyAsync(blk.data(), M.arout, sizeof(double) * blk.size(), hipMemcpyDeviceToHost, c.stream));
     MCX_HIP(hipEventRecord(c.ev_chunk[0], c.stream));
     if ((rc = comm_wait(c, c.ev_chunk[0], "multigrid coarsest operator (all-reduced blocks)"))) return rc;
     MCX_HIP(hipStreamSynchronize(c.stream));
+  } else if (v.f32) {  // the float blocks, widened on the host
+    std::vector<float> blk32(blk.size());
+    MCX_HIP(hipMemcpyAsync(blk32.data(), v.A.as<float>(), sizeof(float) * blk32.size(), hipMemcpyDeviceToHost, c.stream));
+    MCX_HIP(hipStreamSynchronize(c.stream));
+    for (size_t q = 0; q < blk.size(); q++) blk[q] = blk32[q];
   } else {
-    MCX_HIP(hipMemcpyAsync(blk.data(), v.A, sizeof(double) * blk.size(), hipMemcpyDeviceToHost, c.stream));
+    MCX_HIP(hipMemcpyAsync(blk.data(), v.A.as<double>(), sizeof(double) * blk.size(), hipMemcpyDeviceToHost, c.stream));
     MCX_HIP(hipStreamSynchronize(c.stream));
   }
   for (int64_t p = 0; p < nn; p++) {
@@ -365,7 +385,7 @@ int pcmg_ensure(Ctx& c) {
     PcmgLevel &f = M.L[l], &k = M.L[l + 1];
     const PcmgXfer t = xfer(M, l);
     const PcmgLay lx = lay_of(c, l), lc = lay_of(c, l + 1);
-    MCX_HIP(hipMemsetAsync(k.A, 0, sizeof(double) * 243 * k.nn, c.stream));
+    MCX_HIP(hipMemsetAsync(k.A.p, 0, esz(k) * 243 * k.nn, c.stream));
     for (int colour = 0; colour < 27; colour++) {
       if (colour % 3 >= k.N[0] || (colour / 3) % 3 >= k.N[1] || colour / 9 >= k.N[2]) continue;  // no node has it
       for (int d = 0; d < 3; d++) {
@@ -383,7 +403,8 @@ int pcmg_ensure(Ctx& c) {
     launch_pcmg_seed(c, lx, v.nn, v.x);
     double nrm = 0.;
     for (int it = 0; it < 10; it++) {
-      if ((rc = apply_level(c, l, nullptr)) || (rc = launch_pcmg_scale_dot(c, v.nn, v.dinv, v.r, v.d))) return rc;
+      if ((rc = apply_level(c, l, nullptr)) || (rc = launch_pcmg_scale_dot(c, v.nn, v.dinv, v.r, v.d)))
+        return rc;
       double s = 0.;
       if ((rc = read_red(c, 1, &s))) return rc;
       nrm = std::sqrt(s);
@@ -405,7 +426,7 @@ int pcmg_ensure(Ctx& c) {
 
 // Chebyshev of degree k on D^-1 A over [0.1, 1.1] lmax (the recurrence of PETSc's KSPCHEBYSHEV,
 // written for the increment d = x_new - x)
-static int smooth(Ctx& c, int l, const double* b, bool xzero) {
+static int smooth(Ctx& c, int l, PcmgVec b, bool xzero) {
   PcmgLevel& v = c.mg.L[l];
   const PcmgLay lx = lay_of(c, l);
   const double emin = .1 * v.lmax, emax = 1.1 * v.lmax;
@@ -416,8 +437,8 @@ static int smooth(Ctx& c, int l, const double* b, bool xzero) {
     if (!skip)
       if (int rc = apply_level(c, l, b)) return rc;
     // level 0: v.r = A x, the kernel subtracts; coarser levels: v.r = b - A x already
-    const double* rb = skip || l == 0 ? b : v.r;
-    const double* rw = !skip && l == 0 ? v.r : nullptr;
+    const PcmgVec rb = skip || l == 0 ? b : v.r;
+    const PcmgVec rw = !skip && l == 0 ? v.r : PcmgVec();
     if (s == 0) {
       launch_pcmg_cheb(c, lx, v.nn, rb, rw, v.dinv, v.d, v.x, 0., scale, true, xzero);
     } else {
@@ -434,7 +455,7 @@ static int smooth(Ctx& c, int l, const double* b, bool xzero) {
 // application, one of the masked residual before P^T and one of the coarse correction before P; the
 // coarsest level is one all-reduce of its right-hand side, the dense product on every rank, and each
 // rank's box of the result, ghosts included
-static int cycle(Ctx& c, int l, const double* b) {
+static int cycle(Ctx& c, int l, PcmgVec b) {
   Pcmg& M = c.mg;
   PcmgLevel& v = M.L[l];
   int rc = 0;
@@ -477,7 +498,7 @@ int pcmg_solve(Ctx& c, int* its_out, double* rnorm, int* reason_out) {
   const Geo& g = c.g;
   const int64_t nown3 = 3 * (int64_t)g.nown, npad3 = (int64_t)g.PX * g.PY * g.PZ * 3;
   const PcmgLay lp = pcmg_lay_pad(c);
-  double* z = c.mg.L[0].x;
+  double* z = c.mg.L[0].x.as<double>();
   const double rtol = c.o.ksp_rtol, abstol = c.o.ksp_abstol, dtol = c.o.ksp_dtol;
   const int maxits = c.o.ksp_max_it;
   std::vector<double> hist;

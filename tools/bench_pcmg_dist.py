@@ -8,7 +8,8 @@ iteration (counted from the cycle's definition).
 
 The in-process transport serialises the ranks on one device: its time per iteration says nothing
 about as many GPUs.  What carries over is the iteration count, the memory and the counts of
-collectives."""
+collectives.  --precision single keeps the coarse levels in float (-pc_mg_precision single); both
+runs the double and the single hierarchy one after the other on the same contexts ("mg", "mg_single")."""
 import argparse
 import json
 import os
@@ -30,6 +31,8 @@ ap.add_argument("--levels", type=int, default=0, help="pc_mg_levels (0: automati
 ap.add_argument("--smooth", type=int, default=2, help="pc_mg_smooth (Chebyshev degree)")
 ap.add_argument("--no-jacobi", action="store_true", help="skip the Jacobi solves (thousands of iterations at 512^3)")
 ap.add_argument("--comm-timeout", type=float, default=300.0)
+ap.add_argument("--precision", default="double", choices=["double", "single", "both"],
+                help="pc_mg_precision; both: the two hierarchies one after the other on these contexts")
 a = ap.parse_args()
 g = [int(v) for v in a.grid.split("x")]
 g = g * 3 if len(g) == 1 else g
@@ -37,6 +40,7 @@ p = [int(v) for v in a.procs.split("x")]
 nr = p[0] * p[1] * p[2]
 argv = ["-da_grid_x", g[0], "-da_grid_y", g[1], "-da_grid_z", g[2], "-da_processors_x", p[0], "-da_processors_y", p[1],
         "-da_processors_z", p[2], "-bc_type", a.bc_type, "-ksp_rtol", repr(a.rtol)]
+PRECISIONS = {"double": [0], "single": [1], "both": [0, 1]}[a.precision]
 group = M.LocalGroup(nr)
 out, errors = [None] * nr, []
 
@@ -64,14 +68,18 @@ def rank_main(r):
             m.set_option("pc_mg_levels", a.levels)
             m.set_option("pc_mg_smooth", a.smooth)
             m.set_option("pc_type", 1)
-            t0 = time.perf_counter()
-            o["its"], o["rnorm"], o["reason"] = m.solve_Ax()  # builds the hierarchy
-            o["wall_first"] = (time.perf_counter() - t0) * 1e3
-            o["ms_first"] = m.timing()["solve_ms"]
-            o["its2"] = m.solve_Ax()[0]
-            o["ms_mg"] = m.timing()["solve_ms"]
-            o["du"] = m.du()
-            o["info"] = m.pc_mg_info()
+            o["mg"] = {}
+            for single in PRECISIONS:
+                q = o["mg"][single] = {}
+                m.set_option("pc_mg_precision", single)  # a change frees the hierarchy: the next solve builds it
+                t0 = time.perf_counter()
+                q["its"], q["rnorm"], q["reason"] = m.solve_Ax()  # builds the hierarchy
+                q["wall_first"] = (time.perf_counter() - t0) * 1e3
+                q["ms_first"] = m.timing()["solve_ms"]
+                q["its2"] = m.solve_Ax()[0]
+                q["ms_mg"] = m.timing()["solve_ms"]
+                q["du"] = m.du()
+                q["info"] = m.pc_mg_info()
             o["box1"] = [int(v) for v in m.pc_mg_box(1)[1]]
             out[r] = o
         finally:
@@ -88,31 +96,46 @@ for t in ts:
 if errors:
     sys.exit(f"bench_pcmg_dist: {errors}")
 group.destroy()
-o0, info = out[0], out[0]["info"]
-L, k = info["levels"], a.smooth
+k = a.smooth
+
+
+def mg_line(single):
+    qs = [o["mg"][single] for o in out]
+    q0, info = qs[0], qs[0]["info"]
+    L = info["levels"]
+    return {"precision": "single" if single else "double", "its": q0["its"], "reason": q0["reason"], "rnorm": q0["rnorm"],
+            "levels": L, "nxyz": info["nxyz"].tolist(),
+            "lmax": info["lmax"].tolist(), "smooth": k, "setup_ms": max(q["ms_first"] - q["ms_mg"] for q in qs),
+            "first_solve_ms": max(q["ms_first"] for q in qs), "first_solve_wall_ms": max(q["wall_first"] for q in qs),
+            "solve_ms": max(q["ms_mg"] for q in qs), "ms_per_it": max(q["ms_mg"] for q in qs) / max(q0["its2"], 1),
+            "same_on_every_rank": all((q["its"], q["rnorm"], q["reason"]) == (q0["its"], q0["rnorm"], q0["reason"]) for q in qs),
+            "hierarchy_bytes_per_rank": [q["info"]["bytes"] for q in qs], "level1_box_per_rank": [o["box1"] for o in out],
+            # per PCG iteration: every smoothed level fills x's ghosts before each of its 2k operator
+            # applications (k - 1 in the pre-smoother, the residual, k in the post-smoother), the masked
+            # residual's before P^T and, unless the coarsest level sits below, the correction's before P; the
+            # search direction's before the fine SpMV.  All-reduces: r.z, p.Ap and the coarsest right-hand side
+            "halo_exchanges_per_it": (L - 1) * (2 * k + 1) + (L - 2) + 1, "allreduces_per_it": 3}
+
+
 line = {
     "workload": f"{g[0]}x{g[1]}x{g[2]} nodes over {p[0]}x{p[1]}x{p[2]} ranks (in-process transport, one GPU), time step 1, "
                 f"elastic, bc_type {a.bc_type}, rtol {a.rtol:g}",
-    "mg": {"its": o0["its"], "reason": o0["reason"], "rnorm": o0["rnorm"], "levels": L, "nxyz": info["nxyz"].tolist(),
-           "lmax": info["lmax"].tolist(), "smooth": k, "setup_ms": max(o["ms_first"] - o["ms_mg"] for o in out),
-           "first_solve_ms": max(o["ms_first"] for o in out), "first_solve_wall_ms": max(o["wall_first"] for o in out),
-           "solve_ms": max(o["ms_mg"] for o in out), "ms_per_it": max(o["ms_mg"] for o in out) / max(o0["its2"], 1),
-           "same_on_every_rank": all((o["its"], o["rnorm"], o["reason"]) == (o0["its"], o0["rnorm"], o0["reason"]) for o in out),
-           "hierarchy_bytes_per_rank": [o["info"]["bytes"] for o in out], "level1_box_per_rank": [o["box1"] for o in out],
-           # per PCG iteration: every smoothed level fills x's ghosts before each of its 2k operator
-           # applications (k - 1 in the pre-smoother, the residual, k in the post-smoother), the masked
-           # residual's before P^T and, unless the coarsest level sits below, the correction's before P; the
-           # search direction's before the fine SpMV.  All-reduces: r.z, p.Ap and the coarsest right-hand side
-           "halo_exchanges_per_it": (L - 1) * (2 * k + 1) + (L - 2) + 1, "allreduces_per_it": 3},
     "device_bytes_per_rank_jacobi": [o["bytes_j"] for o in out],
     "note": "the in-process transport serialises the ranks on one device: ms per iteration is no multi-GPU figure",
 }
+for single in PRECISIONS:
+    line["mg_single" if single else "mg"] = mg_line(single)
+if len(PRECISIONS) == 2:
+    dd, ds = (np.concatenate([o["mg"][s]["du"] for o in out]) for s in PRECISIONS)
+    line["du_single_rel_diff"] = float(np.linalg.norm(ds - dd) / np.linalg.norm(dd))
 if not a.no_jacobi:
+    first = PRECISIONS[0]  # the keys of the one-hierarchy line, as before
     dj = np.concatenate([o["du_j"] for o in out])
-    dm = np.concatenate([o["du"] for o in out])
+    dm = np.concatenate([o["mg"][first]["du"] for o in out])
     ms_j = max(o["ms_j"] for o in out)
-    line["jacobi"] = {"its": o0["its_j"], "reason": o0["reason_j"], "solve_ms": ms_j, "ms_per_it": ms_j / max(o0["its_j"], 1)}
-    line["speedup_solve"] = ms_j / line["mg"]["solve_ms"]
-    line["speedup_first_solve"] = ms_j / line["mg"]["first_solve_ms"]
+    mgl = line["mg_single" if first else "mg"]
+    line["jacobi"] = {"its": out[0]["its_j"], "reason": out[0]["reason_j"], "solve_ms": ms_j, "ms_per_it": ms_j / max(out[0]["its_j"], 1)}
+    line["speedup_solve"] = ms_j / mgl["solve_ms"]
+    line["speedup_first_solve"] = ms_j / mgl["first_solve_ms"]
     line["du_rel_diff"] = float(np.linalg.norm(dm - dj) / np.linalg.norm(dj))
 print(json.dumps(line))
