@@ -344,7 +344,16 @@ int mcx_micro_get_phase(void* ctx, unsigned char* phase, int64_t* n);
  * pool for good; the pool is allocated at the first such point with "micro_nl_slots" slots (0 =
  * default: what fits 2 GiB, at most the local Gauss points).  mcx_homogenize fails when the pool
  * is too small or a cell does not converge; mcx_update_vars commits the histories.  micro_n = 2
- * has no interior unknown: the one-element average of micro_mat_1's (micro_type 1) J2 law. */
+ * has no interior unknown: the one-element average of micro_mat_1's (micro_type 1) J2 law.
+ * "micro_nl_solver" (mcx_set_option; -micro_nl_solver cell|grid through mcx_apply_args): 0 (default)
+ * solves every listed point with one workgroup (micro_n <= 10, <= 20 with "micro_mem" 1); 1 solves
+ * C_hom and the listed points by launches over the whole device, one workgroup per tile of 8x8x8
+ * nodes and one launch per phase, 2 <= micro_n <= 64.  The definition, the slots (224 B x 8
+ * (micro_n - 1)^3 each), mcx_micro_nl_get_info and mcx_micro_nl_get_pool are the same; the results
+ * agree with solver 0 to the Newton / CG tolerances, not bit for bit, and are a function of the
+ * strain and the committed history alone.  "micro_mem" is ignored under solver 1;
+ * "micro_grid_poll" sets the CG iterations enqueued between two host reads of the solves' states.
+ * The value changes only while no history slot is in use; other laws accept it without effect. */
 /* per Gauss point (mcx_get_gp_strain's order): path 0 = linear shortcut, 1 = solved; Newton
    iterations, CG iterations (Newton steps and tangent solves together) and the final relative
    Newton residual of the last mcx_homogenize.  Any pointer may be NULL. */
@@ -417,16 +426,16 @@ int mcx_set_timing(void* ctx, int on);
 int mcx_get_timing(void* ctx, mcx_timing* t);
 int mcx_synchronize(void* ctx);
 /* tuning knobs ("spmv_subl": lines per sub-slab of the SpMV sweep, 0 = whole XCD slab; "micro_rtol",
-   "micro_max_it", "micro_mem", "micro_solver", "micro_grid_poll": the micro cell's CG, -mat_law micro; "micro_nl_rtol", "micro_nl_max_it", "micro_nl_slots":
+   "micro_max_it", "micro_mem", "micro_solver", "micro_grid_poll": the micro cell's CG, -mat_law micro; "micro_nl_rtol", "micro_nl_max_it", "micro_nl_slots", "micro_nl_solver":
    -mat_law micro_nl) and a
    device-only SpMV timer (iters launches on the current search direction, HIP events) */
 int mcx_set_option(void* ctx, const char* name, double value);
 /* the command-line flags that have no mcx_opts field, applied to a context through mcx_set_option:
-   -micro_mem lds|device ("micro_mem" 0 | 1), -micro_solver cell|grid ("micro_solver" 0 | 1),
+   -micro_mem lds|device ("micro_mem" 0 | 1), -micro_solver cell|grid ("micro_solver" 0 | 1), -micro_nl_solver cell|grid ("micro_nl_solver" 0 | 1),
    -micro_rtol, -micro_max_it, -micro_nl_rtol, -micro_nl_max_it, -micro_nl_slots (each with a
    number), -pc_type jacobi|mg ("pc_type" 0 | 1), -pc_mg_levels N, -mg_levels_ksp_max_it k
    ("pc_mg_smooth"), -pc_mg_dist 0|1 ("pc_mg_dist"; give it before -pc_type), -pc_mg_precision
-   double|single ("pc_mg_precision" 0 | 1).  mcx_parse_args accepts these flags and checks -micro_mem's, -micro_solver's and -pc_mg_precision's word; call this after mcx_init with the same argv.  Other flags are skipped. */
+   double|single ("pc_mg_precision" 0 | 1).  mcx_parse_args accepts these flags and checks -micro_mem's, -micro_solver's, -micro_nl_solver's and -pc_mg_precision's word; call this after mcx_init with the same argv.  Other flags are skipped. */
 int mcx_apply_args(void* ctx, int argc, const char* const* argv);
 int mcx_time_spmv(void* ctx, int iters, double* avg_ms);
 

@@ -399,6 +399,7 @@ using namespace mcx;
 // mcx_opts fields: mcx_parse_args accepts them, mcx_apply_args applies them after mcx_init
 static const char* const kApplyFlags[] = {"-micro_mem",     "-micro_rtol",      "-micro_max_it",  "-micro_nl_rtol",
                                           "-micro_nl_max_it", "-micro_nl_slots", "-micro_solver",
+                                          "-micro_nl_solver",
                                           "-pc_type",       "-pc_mg_levels",    "-mg_levels_ksp_max_it",
                                           "-pc_mg_dist",    "-pc_mg_precision"};
 static bool apply_flag(const char* k) {
@@ -532,6 +533,10 @@ int mcx_parse_args(mcx_opts* o, int argc, const char* const* argv) try {
       }
       if (!std::strcmp(k, "-micro_solver") && (!v || (std::strcmp(v, "cell") && std::strcmp(v, "grid")))) {
         set_error(std::string("-micro_solver: cell or grid, got ") + (v ? v : "(none)"));
+        return 2;
+      }
+      if (!std::strcmp(k, "-micro_nl_solver") && (!v || (std::strcmp(v, "cell") && std::strcmp(v, "grid")))) {
+        set_error(std::string("-micro_nl_solver: cell or grid, got ") + (v ? v : "(none)"));
         return 2;
       }
       if (!std::strcmp(k, "-pc_mg_precision") && (!v || (std::strcmp(v, "double") && std::strcmp(v, "single")))) {
@@ -866,10 +871,12 @@ static MicroNlArgs mnl_args(const Ctx& c) {
 
 // the grid-wide solver (option micro_solver 1) serves -mat_law micro only
 static bool micro_grid(const Ctx& c) { return c.micro_solver == 1 && c.mat.law == MCX_LAW_MICRO; }
+// the grid-wide solver of -mat_law micro_nl (option micro_nl_solver 1): C_hom and the listed points
+static bool micro_nl_grid(const Ctx& c) { return c.mnl_solver == 1 && c.mat.law == MCX_LAW_MICRO_NL; }
 
 // the largest micro_n of the solver and memory mode in use (options micro_solver, micro_mem)
 static int micro_nmax(const Ctx& c) {
-  return micro_grid(c) ? MICRO_NMAX_GRID : c.micro_mem ? MICRO_NMAX_DEV : MICRO_NMAX;
+  return micro_grid(c) ? MICRO_NMAX_GRID : micro_nl_grid(c) ? MICRO_NMAX_NL_GRID : c.micro_mem ? MICRO_NMAX_DEV : MICRO_NMAX;
 }
 
 static int micro_n_refused(const Ctx& c) {
@@ -879,6 +886,8 @@ static int micro_n_refused(const Ctx& c) {
                   std::to_string(micro_nmax(c));
   if (micro_grid(c))
     e += " (option micro_solver 1: one workgroup per tile of 8x8x8 nodes, the CG state in device memory)";
+  else if (micro_nl_grid(c))
+    e += " (option micro_nl_solver 1: one workgroup per tile of 8x8x8 nodes; a history slot is 224 B x 8 (micro_n - 1)^3)";
   else if (c.micro_mem)
     e += " (option micro_mem 1: one workgroup per cell with its CG state in device memory)";
   else
@@ -909,8 +918,23 @@ static int micro_resize(Ctx& c, double** p, int64_t* bytes, int64_t want) {
 // enqueues micro_grid_poll gated iterations at a time and reads the six done flags back; the
 // device stops every load case by itself (converged, !(pq > 0), max_it), so what is enqueued past
 // that changes nothing and the results do not depend on micro_grid_poll.
+// solves of micro_nl_solver 1 that share a launch: what keeps the vectors within 512 MiB, at most 64 and
+// at most the local Gauss points (64 from n = 2 to 33, 13 at n = 64); micro_mem_blocks > 0 replaces it
+static int64_t mnl_grid_batch(const Ctx& c) {
+  const int64_t n = c.micro.n, per = (int64_t)sizeof(double) * MNLG_NVEC * 3 * n * n * n;
+  const int64_t b = c.mnl_ws_blocks_opt > 0 ? c.mnl_ws_blocks_opt : std::min<int64_t>(64, ((int64_t)512 << 20) / per);
+  return std::max<int64_t>(1, std::min<int64_t>(b, std::max<int64_t>(1, 8 * c.g.nelem)));
+}
+
+// the grid-wide solvers' one workspace: the six unit-strain solves' layout (mg_layout), and under
+// micro_nl_solver 1 the listed points' (mnlg_layout) in the same memory at another time
+static int64_t grid_ws_bytes(const Ctx& c) {
+  const int64_t lin = mg_ws_bytes(c.micro.n);
+  return micro_nl_grid(c) ? std::max(lin, mnlg_ws_bytes(c.micro.n, mnl_grid_batch(c))) : lin;
+}
+
 static int solve_micro_grid(Ctx& c, const MicroArgs& m) {
-  if (int rc = micro_resize(c, &c.micro_grid_ws, &c.micro_grid_bytes, mg_ws_bytes(m.n))) return rc;
+  if (int rc = micro_resize(c, &c.micro_grid_ws, &c.micro_grid_bytes, grid_ws_bytes(c))) return rc;
   const MicroGridWs w = mg_layout(c.micro_grid_ws, m.n);
   launch_mg_setup(c, m, w);
   MCX_HIP(hipGetLastError());
@@ -946,9 +970,14 @@ static int ensure_micro(Ctx& c) {
         (rc = micro_resize(c, &c.mnl_conc, &c.mnl_conc_bytes, (int64_t)sizeof(double) * MNL_CONC * nmgp)))
       return rc;
   }
-  if (micro_grid(c)) {  // the same six results in micro_out, by the grid-wide solver
+  if (micro_grid(c) || micro_nl_grid(c)) {  // the same six results in micro_out, by the grid-wide solver
     if (int rc = micro_resize(c, &c.micro_ws, &c.micro_ws_bytes, 0)) return rc;
     if (int rc = solve_micro_grid(c, m)) return rc;
+    if (micro_nl_grid(c)) {  // the linear test superposes the six fields: x of every load case
+      const MicroGridWs w = mg_layout(c.micro_grid_ws, m.n);
+      MCX_HIP(hipMemcpy2DAsync(c.mnl_ufield, sizeof(double) * ndof, w.vec, sizeof(double) * 5 * ndof, sizeof(double) * ndof,
+                               6, hipMemcpyDeviceToDevice, c.stream));
+    }
   } else {
     const int64_t rve_ws = c.micro_mem ? (int64_t)sizeof(double) * 6 * 5 * ndof : 0;  // micro_mem 1: six workspaces
     if (int rc = micro_resize(c, &c.micro_ws, &c.micro_ws_bytes, rve_ws)) return rc;
@@ -990,6 +1019,41 @@ static int ensure_micro(Ctx& c) {
 static int64_t mnl_slot_bytes(const Ctx& c) {
   const int64_t ne = c.micro.n - 1;
   return (int64_t)sizeof(double) * MNL_WS * 8 * ne * ne * ne;
+}
+
+// option micro_nl_solver 1: the nsolve listed points, mnl_grid_batch at a time, as launches
+// over the whole device.  Per batch the host enqueues one transition (a CG has ended or not begun:
+// the next Newton step, the next tangent column or the end) and up to micro_grid_poll gated CG
+// iterations, then reads the records back; the device steps every solve through k_mnl_solve's
+// loop by itself and counts its own iterations, so what is enqueued for a solve in another stage
+// changes nothing and the results do not depend on micro_grid_poll or on the batch.
+static int solve_mnl_grid(Ctx& c, const MicroNlArgs& a, int nsolve) {
+  const int64_t batch = mnl_grid_batch(c);
+  if (int rc = micro_resize(c, &c.micro_grid_ws, &c.micro_grid_bytes, grid_ws_bytes(c))) return rc;
+  const MnlGridWs w = mnlg_layout(c.micro_grid_ws, a.m.n, batch);
+  const int per = std::max(1, std::min(c.micro_grid_poll, a.m.max_it));
+  // a solve has at most nl_max_it + 1 state passes and six columns, each CG at most max_it iterations
+  const int64_t max_rounds = (int64_t)(a.nl_max_it + 8) * ((int64_t)(std::max(a.m.max_it, 1) + per - 1) / per + 1);
+  std::vector<MnlGridState> h((size_t)batch);
+  for (int base = 0; base < nsolve; base += (int)batch) {
+    const int cnt = (int)std::min<int64_t>(batch, nsolve - base);
+    launch_mnlg_start(c, w, base, cnt);
+    for (int64_t round = 0;; round++) {
+      launch_mnlg_transition(c, a, w, cnt);
+      for (int q = 0; q < per; q++) launch_mnlg_iterate(c, a, w, cnt);
+      MCX_HIP(hipGetLastError());
+      MCX_HIP(hipMemcpyAsync(h.data(), w.st, sizeof(MnlGridState) * cnt, hipMemcpyDeviceToHost, c.stream));
+      MCX_HIP(hipStreamSynchronize(c.stream));
+      bool done = true;
+      for (int s = 0; s < cnt; s++) done = done && h[s].stage == MNLG_DONE;
+      if (done) break;
+      if (round >= max_rounds) {
+        set_error("-mat_law micro_nl: micro_nl_solver 1 did not end within its iteration limits (internal error)");
+        return 35;
+      }
+    }
+  }
+  return 0;
 }
 
 static int micro_nl_homogenize(Ctx& c) {
@@ -1034,7 +1098,7 @@ static int micro_nl_homogenize(Ctx& c) {
     MCX_HIP(hipMemsetAsync(c.mnl_pool, 0, (size_t)(c.mnl_cap * bytes), c.stream));
     c.device_bytes += c.mnl_cap * bytes;
   }
-  {  // micro_mem 1: one workspace of 6 nodal vectors per resident block (two blocks per compute unit)
+  if (!micro_nl_grid(c)) {  // micro_mem 1: one workspace of 6 nodal vectors per resident block (two blocks per compute unit)
     c.mnl_ws_blocks = (int)std::min<int64_t>(c.mnl_ws_blocks_opt > 0 ? c.mnl_ws_blocks_opt : 2 * (int64_t)c.ncu, ngp);
     const int64_t nn = (int64_t)a.m.n * a.m.n * a.m.n;
     if (int rc = micro_resize(c, &c.mnl_ws, &c.mnl_ws_bytes,
@@ -1042,7 +1106,12 @@ static int micro_nl_homogenize(Ctx& c) {
       return rc;
   }
   c.mnl_used += h[0];
-  launch_mnl_solve(c, a, h[1]);
+  if (micro_nl_grid(c)) {
+    if (int rc = micro_resize(c, &c.mnl_ws, &c.mnl_ws_bytes, 0)) return rc;
+    if (int rc = solve_mnl_grid(c, a, h[1])) return rc;
+  } else {
+    launch_mnl_solve(c, a, h[1]);
+  }
   MCX_HIP(hipGetLastError());
   MCX_HIP(hipMemcpyAsync(h, c.mnl_cnt, sizeof(h), hipMemcpyDeviceToHost, c.stream));
   MCX_HIP(hipStreamSynchronize(c.stream));
@@ -2198,6 +2267,25 @@ int mcx_set_option(void* ctx, const char* name, double value) try {
     if (!c.micro_solver) return micro_resize(c, &c.micro_grid_ws, &c.micro_grid_bytes, 0);
     return 0;
   }
+  if (!std::strcmp(name, "micro_nl_solver")) {  // who solves the cells of -mat_law micro_nl
+    if (value != 0. && value != 1.) {
+      set_error("micro_nl_solver: 0 (one workgroup per Gauss point, micro_n <= " + std::to_string(MICRO_NMAX) + " / " +
+                std::to_string(MICRO_NMAX_DEV) + " by micro_mem) or 1 (grid-wide, one workgroup per tile, micro_n <= " +
+                std::to_string(MICRO_NMAX_NL_GRID) + ")");
+      return 1;
+    }
+    if ((int)value == c.mnl_solver) return 0;
+    if (c.mnl_used > 0) {  // the histories would outlive the solver that wrote them
+      set_error("micro_nl_solver: " + std::to_string(c.mnl_used) +
+                " history slots are in use; the solver is chosen before the first non-linear point");
+      return 2;
+    }
+    c.mnl_solver = (int)value;
+    if (c.mat.law != MCX_LAW_MICRO_NL) return 0;  // accepted, no effect
+    c.micro_dirty = true;  // C_hom and the concentration tensors are recomputed by the other solver
+    if (!c.mnl_solver) return micro_resize(c, &c.micro_grid_ws, &c.micro_grid_bytes, 0);
+    return 0;
+  }
   if (!std::strcmp(name, "pc_mg_dist")) {  // 1: pc_type 1 on a context with a communicator (the distributed hierarchy)
     if (value != 0. && value != 1.) {
       set_error("pc_mg_dist: 0 (pc_type mg on one rank only) or 1 (the hierarchy distributed over the ranks)");
@@ -2668,6 +2756,12 @@ int mcx_apply_args(void* ctx, int argc, const char* const* argv) try {
     } else if (!std::strcmp(k, "-micro_solver")) {
       if (std::strcmp(v, "cell") && std::strcmp(v, "grid")) {
         set_error(std::string("-micro_solver: cell or grid, got ") + v);
+        return 2;
+      }
+      value = std::strcmp(v, "grid") ? 0. : 1.;
+    } else if (!std::strcmp(k, "-micro_nl_solver")) {
+      if (std::strcmp(v, "cell") && std::strcmp(v, "grid")) {
+        set_error(std::string("-micro_nl_solver: cell or grid, got ") + v);
         return 2;
       }
       value = std::strcmp(v, "grid") ? 0. : 1.;

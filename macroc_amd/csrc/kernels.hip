@@ -1797,6 +1797,483 @@ __global__ __launch_bounds__(MICRO_TPB) void k_mg_out(MicroGridWs w, int cnt, do
   }
 }
 
+// ---------------------------------------------------------------------------- grid-wide non-linear micro cell
+// option micro_nl_solver 1: k_mnl_solve's Newton / CG / tangent loop, statement for
+// statement, with every listed point spread over the device: blockIdx.x = a tile of MG_T^3 nodes
+// (gather) or elements (Gauss-point pass) or a block of dofs, blockIdx.y = the solve of the batch.
+// The loop's control flow lives in the solve's state record (MnlGridState): every kernel first
+// reads the record's stage, written by a scalar kernel of an earlier launch, and returns unless
+// the stage is its own, so the host enqueues one fixed sequence for solves in different states
+// and whatever is enqueued past a solve's end changes nothing.  Nothing waits, spins or uses a
+// floating-point atomic; the sums are taken tile by tile (micro_reduce2's tree) and then over the
+// tiles in ascending order strided over 512 threads, an order that depends on n alone.  The slot,
+// the solve's place in the batch and the block index select memory only.
+__device__ __forceinline__ double* mnlg_vec(const MnlGridWs& w, int s, int v, int64_t ndof) {
+  return w.vec + ((size_t)s * MNLG_NVEC + v) * (size_t)ndof;  // v: 0 u, 1 x, 2 r, 3 p, 4 q, 5 D^-1
+}
+__device__ __forceinline__ double* mnlg_part(const MnlGridWs& w, int s, int q) {
+  return w.part + ((size_t)s * MNLG_NPART + q) * (size_t)w.npart;
+}
+
+// the batch's records: solve s is point list[base + s], about to take its first state pass
+__global__ void k_mnlg_start(MnlGridWs w, const int* __restrict__ list, const int* __restrict__ slot, int base, int cnt) {
+  const int s = blockIdx.x * blockDim.x + threadIdx.x;
+  if (s >= cnt) return;
+  MnlGridState st{};
+  st.q = list[base + s];
+  st.slot = slot[st.q];
+  st.stage = MNLG_TRANS;
+  st.lc = -1;
+  st.fresh = 1;
+  w.st[s] = st;
+}
+
+// one thread per node.  Newton (TSTART false, a solve in transition with lc < 0): u = Eb x on the
+// boundary, 0 inside and D^-1 = 0 before the first state pass, u += x after a step; x = 0.
+// TSTART: x = E_lc x on the boundary, 0 inside (mnl_boundary's statement in both).
+template <bool TSTART>
+__global__ __launch_bounds__(MICRO_TPB) void k_mnlg_prep(MicroNlArgs a, MnlGridWs w, int64_t ngp,
+                                                         const double* __restrict__ eps) {
+  const int s = blockIdx.y;
+  const MnlGridState& st = w.st[s];
+  if (st.stage != (TSTART ? MNLG_TSTART : MNLG_TRANS) || (!TSTART && st.lc >= 0)) return;
+  const int n = a.m.n, ne = n - 1, nn = n * n * n, lc = st.lc;
+  const int nd = blockIdx.x * MICRO_TPB + threadIdx.x;
+  if (nd >= nn) return;
+  const int64_t ndof = 3 * (int64_t)nn;
+  double* const su = mnlg_vec(w, s, 0, ndof);
+  double* const sx = mnlg_vec(w, s, 1, ndof);
+  if (!TSTART && !st.fresh) {
+#pragma unroll
+    for (int r = 0; r < 3; r++) {
+      su[3 * (size_t)nd + r] += sx[3 * (size_t)nd + r];
+      sx[3 * (size_t)nd + r] = 0.;
+    }
+    return;
+  }
+  double Eb[3][3];
+  if (TSTART) {
+    const int p = lc == 5 ? 1 : 0, p2 = lc == 3 ? 1 : 2;  // xy: (0, 1), xz: (0, 2), yz: (1, 2)
+#pragma unroll
+    for (int r = 0; r < 3; r++)
+#pragma unroll
+      for (int d = 0; d < 3; d++)
+        Eb[r][d] = lc < 3 ? ((r == lc && d == lc) ? 1. : 0.) : (((r == p && d == p2) || (r == p2 && d == p)) ? 0.5 : 0.);
+  } else {
+    double em[6];
+#pragma unroll
+    for (int l = 0; l < 6; l++) em[l] = eps[l * ngp + st.q];
+    Eb[0][0] = em[0], Eb[0][1] = em[3] / 2., Eb[0][2] = em[4] / 2.;
+    Eb[1][0] = em[3] / 2., Eb[1][1] = em[1], Eb[1][2] = em[5] / 2.;
+    Eb[2][0] = em[4] / 2., Eb[2][1] = em[5] / 2., Eb[2][2] = em[2];
+  }
+  const int i = nd % n, j = (nd / n) % n, k = nd / (n * n);
+  const bool bnd = i == 0 || j == 0 || k == 0 || i == ne || j == ne || k == ne;
+  const double X[3] = {(double)i / (double)ne, (double)j / (double)ne, (double)k / (double)ne};
+#pragma unroll
+  for (int r = 0; r < 3; r++) {
+    const double v = bnd ? Eb[r][0] * X[0] + Eb[r][1] * X[1] + Eb[r][2] * X[2] : 0.;
+    if (TSTART) {
+      sx[3 * (size_t)nd + r] = v;
+    } else {
+      su[3 * (size_t)nd + r] = v;
+      sx[3 * (size_t)nd + r] = 0.;
+      mnlg_vec(w, s, 5, ndof)[3 * (size_t)nd + r] = 0.;
+    }
+  }
+}
+
+// mnl_strain on the staged nodes: sv is component-major, [3][(MG_T + 1)^3], (ei, ej, ek) the
+// element's node 0 in the tile; the same products and sums in the same order
+__device__ __forceinline__ void mnlg_strain(const double* __restrict__ dn, const double* __restrict__ sv, int ei, int ej,
+                                            int ek, double (&eps)[6]) {
+  constexpr int P = MG_T + 1, P3 = P * P * P;
+  double G[3][3] = {{0., 0., 0.}, {0., 0., 0.}, {0., 0., 0.}};  // G[r][d] = d u_r / d x_d
+#pragma unroll 1
+  for (int a = 0; a < 8; a++) {
+    const int hb = (ei + (a & 1)) + P * ((ej + (a >> 1 & 1)) + P * (ek + (a >> 2)));
+#pragma unroll
+    for (int r = 0; r < 3; r++)
+#pragma unroll
+      for (int d = 0; d < 3; d++) G[r][d] += dn[3 * a + d] * sv[r * P3 + hb];
+  }
+  eps[0] = G[0][0];
+  eps[1] = G[1][1];
+  eps[2] = G[2][2];
+  eps[3] = G[0][1] + G[1][0];
+  eps[4] = G[0][2] + G[2][0];
+  eps[5] = G[1][2] + G[2][1];
+}
+
+// The Gauss-point pass over a tile of MG_T^3 elements (those whose node 0 the tile holds).  The
+// workgroup stages the (MG_T + 1)^3 nodes of these elements of the source vector in LDS
+// (component-major: the 8 lanes of an element read one address, the 8 elements of a wave
+// consecutive ones), then walks the tile's MG_T layers: thread t has Gauss point t & 7 of element
+// (t >> 3 & 7, t >> 6) of the layer, so a wave's slot traffic is 64 consecutive doubles.
+//   WHICH 0  a CG iteration: work stresses = C_gp B p from the slot's tangent data
+//   WHICH 1  a transition: lc < 0 the state at the iterate u (j2_point on the committed history:
+//            stresses, new history, tangent data, trial f), lc >= 0 the stresses C_gp B x of the
+//            column's solution; the tile's six stress sums (times detJ) and its largest f
+//   WHICH 2  the start of a tangent solve: C_gp B x of the boundary values
+template <int WHICH>
+__global__ __launch_bounds__(MICRO_TPB) void k_mnlg_gp(MicroNlArgs a, MnlGridWs w, double* __restrict__ pool) {
+  constexpr int P = MG_T + 1, P3 = P * P * P;
+  __shared__ double sv[3 * P3];
+  __shared__ double sdn[8 * 24];
+  __shared__ double sred[2 * (MICRO_TPB / 64)];
+  const int tid = threadIdx.x, s = blockIdx.y;
+  const MnlGridState& st = w.st[s];
+  if (st.stage != (WHICH == 0 ? MNLG_CG : WHICH == 1 ? MNLG_TRANS : MNLG_TSTART)) return;  // the whole workgroup
+  const bool res = WHICH == 1 && st.lc < 0;
+  const int n = a.m.n, ne = n - 1, nel = ne * ne * ne, nmgp = 8 * nel, nt = w.ntile, tile = blockIdx.x;
+  const int64_t ndof = 3 * (int64_t)n * n * n;
+  const int ox = MG_T * (tile % nt), oy = MG_T * ((tile / nt) % nt), oz = MG_T * (tile / (nt * nt));
+  const double* const src = mnlg_vec(w, s, WHICH == 0 ? 3 : (res ? 0 : 1), ndof);
+  double* const ws = pool + (size_t)st.slot * MNL_WS * nmgp;
+  const double detJ = 1. / (8. * (double)nel);
+  const double Gp[2] = {a.m.E[0] / (2. * (1. + a.m.nu[0])), a.m.E[1] / (2. * (1. + a.m.nu[1]))};
+  const double Kp[2] = {a.m.E[0] / (3. * (1. - 2. * a.m.nu[0])), a.m.E[1] / (3. * (1. - 2. * a.m.nu[1]))};
+  for (int t = tid; t < 8 * 24; t += MICRO_TPB) sdn[t] = mnl_dn(t, ne);
+  for (int h = tid; h < P3; h += MICRO_TPB) {
+    const int gi = ox + h % P, gj = oy + (h / P) % P, gk = oz + h / (P * P);
+    const bool in = gi < n && gj < n && gk < n;
+    const size_t nd = in ? (size_t)gi + (size_t)n * ((size_t)gj + (size_t)n * (size_t)gk) : 0;
+#pragma unroll
+    for (int r = 0; r < 3; r++) sv[r * P3 + h] = in ? src[3 * nd + r] : 0.;
+  }
+  __syncthreads();
+  const int gp = tid & 7, lx = (tid >> 3) & 7, ly = tid >> 6, ei = ox + lx, ej = oy + ly;
+  double sg[6] = {0., 0., 0., 0., 0., 0.}, fmax = -1e300;
+  if (ei < ne && ej < ne) {
+#pragma unroll 1
+    for (int lz = 0; lz < MG_T; lz++) {
+      const int ek = oz + lz;
+      if (ek >= ne) break;
+      const int ph = micro_phase(a.m.type, ne, ei, ej, ek);
+      const size_t mg = 8 * ((size_t)ei + (size_t)ne * ((size_t)ej + (size_t)ne * (size_t)ek)) + gp;
+      double ee[6], nv[6], sgm[6], th, thb;
+      mnlg_strain(sdn + 24 * gp, sv, lx, ly, lz, ee);
+      if (res) {
+        double h[7], hn[7];
+#pragma unroll
+        for (int i = 0; i < 7; i++) h[i] = ws[(size_t)(MNL_H0 + i) * nmgp + mg];
+        const double f = j2_point(ph ? Gp[1] : Gp[0], ph ? Kp[1] : Kp[0], ph ? a.Sy[1] : a.Sy[0],
+                                  ph ? a.Ka[1] : a.Ka[0], ee, h, sgm, hn, th, thb, nv);
+        fmax = f > fmax ? f : fmax;
+#pragma unroll
+        for (int i = 0; i < 7; i++) ws[(size_t)(MNL_H1 + i) * nmgp + mg] = hn[i];
+        ws[(size_t)MNL_TAN * nmgp + mg] = th;
+        ws[(size_t)(MNL_TAN + 1) * nmgp + mg] = thb;
+#pragma unroll
+        for (int b = 0; b < 6; b++) ws[(size_t)(MNL_TAN + 2 + b) * nmgp + mg] = nv[b];
+      } else {
+        th = ws[(size_t)MNL_TAN * nmgp + mg];
+        thb = ws[(size_t)(MNL_TAN + 1) * nmgp + mg];
+#pragma unroll
+        for (int b = 0; b < 6; b++) nv[b] = ws[(size_t)(MNL_TAN + 2 + b) * nmgp + mg];
+        mnl_Cmul(ph ? Gp[1] : Gp[0], ph ? Kp[1] : Kp[0], th, thb, nv, ee, sgm);
+      }
+#pragma unroll
+      for (int k = 0; k < 6; k++) {
+        ws[(size_t)(MNL_SIG + k) * nmgp + mg] = sgm[k];
+        if (WHICH == 1) sg[k] += sgm[k] * detJ;
+      }
+    }
+  }
+  if (WHICH == 1) {
+    micro_reduce2(sg[0], sg[1], sred);
+    micro_reduce2(sg[2], sg[3], sred);
+    micro_reduce2(sg[4], sg[5], sred);
+    fmax = mnl_reduce_max(fmax, sred);
+    if (tid == 0) {
+#pragma unroll
+      for (int k = 0; k < 6; k++) mnlg_part(w, s, 2 + k)[tile] = sg[k];
+      mnlg_part(w, s, 8)[tile] = fmax;
+    }
+  }
+}
+
+// mnl_diag with the element's phase computed where it is needed (no phase array at n = 64)
+__device__ __forceinline__ void mnlg_diag(const double* __restrict__ ws, const double* __restrict__ sdn, int type, int n,
+                                          int i, int j, int k, double detJ, const double (&Gp)[2],
+                                          const double (&Kp)[2], double (&dg)[3]) {
+  const int ne = n - 1, nmgp = 8 * ne * ne * ne;
+  dg[0] = dg[1] = dg[2] = 0.;
+#pragma unroll 1
+  for (int oz = 1; oz >= 0; oz--)
+#pragma unroll 1
+    for (int oy = 1; oy >= 0; oy--)
+#pragma unroll 1
+      for (int ox = 1; ox >= 0; ox--) {
+        const int ei = i - ox, ej = j - oy, ek = k - oz;
+        if (ei < 0 || ej < 0 || ek < 0 || ei >= ne || ej >= ne || ek >= ne) continue;
+        const int a = ox + 2 * oy + 4 * oz, e = ei + ne * (ej + ne * ek), ph = micro_phase(type, ne, ei, ej, ek);
+#pragma unroll 1
+        for (int gp = 0; gp < 8; gp++) {
+          const int mg = 8 * e + gp;
+          const double* dn = sdn + 24 * gp + 3 * a;
+          const double th = ws[(size_t)MNL_TAN * nmgp + mg], thb = ws[(size_t)(MNL_TAN + 1) * nmgp + mg];
+          double nv[6];
+#pragma unroll
+          for (int b = 0; b < 6; b++) nv[b] = ws[(size_t)(MNL_TAN + 2 + b) * nmgp + mg];
+          const double bc[3][6] = {{dn[0], 0., 0., dn[1], dn[2], 0.},
+                                   {0., dn[1], 0., dn[0], 0., dn[2]},
+                                   {0., 0., dn[2], 0., dn[0], dn[1]}};
+#pragma unroll
+          for (int r = 0; r < 3; r++) {
+            double sc[6], t = 0.;
+            mnl_Cmul(ph ? Gp[1] : Gp[0], ph ? Kp[1] : Kp[0], th, thb, nv, bc[r], sc);
+#pragma unroll
+            for (int b = 0; b < 6; b++) t += bc[r][b] * sc[b];
+            dg[r] += t * detJ;
+          }
+        }
+      }
+}
+
+// D^-1 of the interior dofs from the tangent data of the first state pass: one thread per node
+__global__ __launch_bounds__(MICRO_TPB) void k_mnlg_diag(MicroNlArgs a, MnlGridWs w, const double* __restrict__ pool) {
+  __shared__ double sdn[8 * 24];
+  const int s = blockIdx.y;
+  const MnlGridState& st = w.st[s];
+  if (st.stage != MNLG_TRANS || st.lc >= 0 || !st.fresh) return;
+  const int n = a.m.n, ne = n - 1, nn = n * n * n, nel = ne * ne * ne;
+  for (int t = threadIdx.x; t < 8 * 24; t += MICRO_TPB) sdn[t] = mnl_dn(t, ne);
+  __syncthreads();
+  const int nd = blockIdx.x * MICRO_TPB + threadIdx.x;
+  if (nd >= nn) return;
+  const int i = nd % n, j = (nd / n) % n, k = nd / (n * n);
+  if (i == 0 || j == 0 || k == 0 || i == ne || j == ne || k == ne) return;
+  const double detJ = 1. / (8. * (double)nel);
+  const double Gp[2] = {a.m.E[0] / (2. * (1. + a.m.nu[0])), a.m.E[1] / (2. * (1. + a.m.nu[1]))};
+  const double Kp[2] = {a.m.E[0] / (3. * (1. - 2. * a.m.nu[0])), a.m.E[1] / (3. * (1. - 2. * a.m.nu[1]))};
+  double dg[3];
+  mnlg_diag(pool + (size_t)st.slot * MNL_WS * (8 * (size_t)nel), sdn, a.m.type, n, i, j, k, detJ, Gp, Kp, dg);
+  double* const sd = mnlg_vec(w, s, 5, 3 * (int64_t)nn);
+#pragma unroll
+  for (int r = 0; r < 3; r++) sd[3 * (size_t)nd + r] = 1. / dg[r];
+}
+
+// The node gather over a tile of MG_T^3 nodes: mnl_gather from the slot's work stresses (the node's
+// elements ascending, their Gauss points ascending).  INIT (a Newton step or a tangent solve
+// starts): r = -(the gathered force) on the interior, p = z = D^-1 r, q = 0, the tile's r.z and
+// z.z; else q = the gathered K_T p on the interior and the tile's p.q.
+template <bool INIT>
+__global__ __launch_bounds__(MICRO_TPB) void k_mnlg_gather(MicroNlArgs a, MnlGridWs w, const double* __restrict__ pool) {
+  __shared__ double sdn[8 * 24];
+  __shared__ double sred[2 * (MICRO_TPB / 64)];
+  const int tid = threadIdx.x, s = blockIdx.y;
+  const MnlGridState& st = w.st[s];
+  if (INIT ? !((st.stage == MNLG_TRANS && st.lc < 0) || st.stage == MNLG_TSTART) : st.stage != MNLG_CG) return;
+  const int n = a.m.n, ne = n - 1, nel = ne * ne * ne, nt = w.ntile, tile = blockIdx.x;
+  const int64_t ndof = 3 * (int64_t)n * n * n;
+  const double detJ = 1. / (8. * (double)nel);
+  const double* const ws = pool + (size_t)st.slot * MNL_WS * (8 * (size_t)nel);
+  for (int t = tid; t < 8 * 24; t += MICRO_TPB) sdn[t] = mnl_dn(t, ne);
+  __syncthreads();
+  const int i = MG_T * (tile % nt) + tid % MG_T, j = MG_T * ((tile / nt) % nt) + (tid / MG_T) % MG_T,
+            k = MG_T * (tile / (nt * nt)) + tid / (MG_T * MG_T);
+  const bool in = i < n && j < n && k < n;
+  const bool bnd = i == 0 || j == 0 || k == 0 || i == ne || j == ne || k == ne;
+  const size_t nd = in ? (size_t)i + (size_t)n * ((size_t)j + (size_t)n * (size_t)k) : 0;
+  double y[3] = {0., 0., 0.};
+  if (in && !bnd) mnl_gather(ws, sdn, n, i, j, k, detJ, y);
+  double s0 = 0., s1 = 0.;
+  if (INIT) {
+    if (in) {
+      double* const sr = mnlg_vec(w, s, 2, ndof);
+      double* const sp = mnlg_vec(w, s, 3, ndof);
+      double* const sq = mnlg_vec(w, s, 4, ndof);
+      const double* const sd = mnlg_vec(w, s, 5, ndof);
+#pragma unroll
+      for (int r = 0; r < 3; r++) {
+        const double rr = bnd ? 0. : -y[r], z = sd[3 * nd + r] * rr;
+        sr[3 * nd + r] = rr;
+        sp[3 * nd + r] = z;
+        sq[3 * nd + r] = 0.;
+        s0 += rr * z;
+        s1 += z * z;
+      }
+    }
+  } else if (in && !bnd) {
+    const double* const sp = mnlg_vec(w, s, 3, ndof);
+    double* const sq = mnlg_vec(w, s, 4, ndof);
+#pragma unroll
+    for (int r = 0; r < 3; r++) {
+      sq[3 * nd + r] = y[r];
+      s0 += sp[3 * nd + r] * y[r];
+    }
+  }
+  micro_reduce2(s0, s1, sred);
+  if (tid == 0) {
+    mnlg_part(w, s, 0)[tile] = s0;
+    if (INIT) mnlg_part(w, s, 1)[tile] = s1;
+  }
+}
+
+// a solve ends: what mcx_micro_nl_get_info reports; the only atomic is the integer count of failed cells
+__device__ __forceinline__ void mnlg_end(MnlGridState& st, int64_t ngp, int* __restrict__ its_out,
+                                         double* __restrict__ rn_out, int* __restrict__ cnt) {
+  its_out[st.q] = st.nits;
+  its_out[ngp + st.q] = st.cgits;
+  its_out[2 * ngp + st.q] = st.status;
+  rn_out[st.q] = st.nrel;
+  if (st.status) atomicAdd(cnt + 2, 1);
+  st.stage = MNLG_DONE;
+}
+
+// The scalar steps, one workgroup per solve: the partials in ascending order strided over the
+// threads, then micro_reduce2's tree; thread 0 carries k_mnl_solve's control flow in the record.
+//   PHASE 0  a transition.  lc < 0: the Newton norm; converged -> sigma, f_trial, the tangent's
+//            first column starts; given up -> ends; else the step's CG starts.  lc >= 0: column lc
+//            from the stress sums; the next column starts, or the symmetrised tangent ends the solve
+//   PHASE 1  after q = K_T p: pq, alpha; !(pq > 0) ends the solve unconverged
+//   PHASE 2  after the x / r update: the iteration count; converged -> the next transition; else beta
+//   PHASE 3  a tangent solve starts: norm0, rz; converged at once when the norm is 0
+template <int PHASE>
+__global__ __launch_bounds__(MICRO_TPB) void k_mnlg_scalar(MicroNlArgs a, MnlGridWs w, int cnt, int64_t ngp,
+                                                           double* __restrict__ sig, double* __restrict__ ctan,
+                                                           double* __restrict__ ftrial, int* __restrict__ its_out,
+                                                           double* __restrict__ rn_out, int* __restrict__ fail) {
+  __shared__ double sred[2 * (MICRO_TPB / 64)];
+  const int tid = threadIdx.x, s = blockIdx.x;
+  MnlGridState& st = w.st[s];
+  if (st.stage != (PHASE == 0 ? MNLG_TRANS : PHASE == 3 ? MNLG_TSTART : MNLG_CG)) return;
+  const double* const p0 = mnlg_part(w, s, 0);
+  const double* const p1 = mnlg_part(w, s, 1);
+  double sa = 0., sb = 0.;
+  if (PHASE != 0 || st.lc < 0)
+    for (int q = tid; q < cnt; q += MICRO_TPB) {
+      sa += p0[q];
+      if (PHASE != 1) sb += p1[q];
+    }
+  micro_reduce2(sa, sb, sred);
+  double sg[6] = {0., 0., 0., 0., 0., 0.}, fmax = -1e300;
+  if (PHASE == 0) {
+#pragma unroll
+    for (int k = 0; k < 6; k++) {
+      const double* const p = mnlg_part(w, s, 2 + k);
+      for (int q = tid; q < cnt; q += MICRO_TPB) sg[k] += p[q];
+    }
+    const double* const pf = mnlg_part(w, s, 8);
+    for (int q = tid; q < cnt; q += MICRO_TPB) fmax = pf[q] > fmax ? pf[q] : fmax;
+    micro_reduce2(sg[0], sg[1], sred);
+    micro_reduce2(sg[2], sg[3], sred);
+    micro_reduce2(sg[4], sg[5], sred);
+    fmax = mnl_reduce_max(fmax, sred);
+  }
+  if (tid != 0) return;
+  if (PHASE == 0) {
+    if (st.lc < 0) {
+      const double norm0 = sqrt(sb);
+      if (st.nits == 0) st.nnorm0 = norm0;
+      st.nrel = st.nnorm0 == 0. ? 0. : norm0 / st.nnorm0;
+      st.fresh = 0;
+      if (st.nnorm0 == 0. || st.nrel <= a.nl_rtol) {
+        // converged: the volume average of the micro stresses (the cell's volume is 1), then the tangent
+#pragma unroll
+        for (int k = 0; k < 6; k++) sig[k * ngp + st.q] = sg[k];
+        ftrial[st.q] = fmax;
+        st.lc = 0;
+        st.stage = MNLG_TSTART;
+      } else if (st.nits >= a.nl_max_it) {
+        st.status = 1;
+        mnlg_end(st, ngp, its_out, rn_out, fail);
+      } else {
+        st.rz = sa;
+        st.norm0 = norm0;
+        st.its = 0;
+        if (0 < a.m.max_it) {
+          st.stage = MNLG_CG;
+        } else {
+          st.status = 2;
+          mnlg_end(st, ngp, its_out, rn_out, fail);
+        }
+      }
+    } else {
+      // column lc of the tangent: the volume average of C_gp B w
+#pragma unroll
+      for (int k = 0; k < 6; k++) st.col[k * 6 + st.lc] = sg[k];
+      if (++st.lc == 6) {
+        for (int t = 0; t < 36; t++) ctan[t * ngp + st.q] = 0.5 * (st.col[t] + st.col[(t % 6) * 6 + t / 6]);
+        mnlg_end(st, ngp, its_out, rn_out, fail);
+      } else {
+        st.stage = MNLG_TSTART;
+      }
+    }
+  } else if (PHASE == 1) {
+    st.pq = sa;
+    if (!(sa > 0.)) {  // no curvature left along p: reported as not converged
+      st.cgits += st.its;
+      st.status = 2;
+      mnlg_end(st, ngp, its_out, rn_out, fail);
+    } else {
+      st.alpha = st.rz / sa;
+    }
+  } else if (PHASE == 2) {
+    st.its++;
+    if (sqrt(sb) / st.norm0 <= a.m.rtol) {
+      st.cgits += st.its;
+      if (st.lc < 0) st.nits++;
+      st.stage = MNLG_TRANS;
+    } else {
+      st.beta = sa / st.rz;
+      st.rz = sa;
+      if (!(st.its < a.m.max_it)) {
+        st.cgits += st.its;
+        st.status = 2;
+        mnlg_end(st, ngp, its_out, rn_out, fail);
+      }
+    }
+  } else {
+    st.rz = sa;
+    st.norm0 = sqrt(sb);
+    st.its = 0;
+    if (st.norm0 == 0.) {
+      st.stage = MNLG_TRANS;  // the boundary values solve the column: no iteration
+    } else if (0 < a.m.max_it) {
+      st.stage = MNLG_CG;
+    } else {
+      st.status = 2;
+      mnlg_end(st, ngp, its_out, rn_out, fail);
+    }
+  }
+}
+
+// x += alpha p, r -= alpha q, z = D^-1 r: one thread per dof, the block's r.z and z.z
+__global__ __launch_bounds__(MICRO_TPB) void k_mnlg_update(MicroNlArgs a, MnlGridWs w) {
+  __shared__ double sred[2 * (MICRO_TPB / 64)];
+  const int s = blockIdx.y;
+  if (w.st[s].stage != MNLG_CG) return;
+  const int64_t ndof = 3 * (int64_t)a.m.n * a.m.n * a.m.n, d = (int64_t)blockIdx.x * MICRO_TPB + threadIdx.x;
+  const double alpha = w.st[s].alpha;
+  double rz = 0., zz = 0.;
+  if (d < ndof) {
+    double* const sx = mnlg_vec(w, s, 1, ndof);
+    double* const sr = mnlg_vec(w, s, 2, ndof);
+    sx[d] += alpha * mnlg_vec(w, s, 3, ndof)[d];
+    const double rr = sr[d] - alpha * mnlg_vec(w, s, 4, ndof)[d], z = mnlg_vec(w, s, 5, ndof)[d] * rr;
+    sr[d] = rr;
+    rz += rr * z;
+    zz += z * z;
+  }
+  micro_reduce2(rz, zz, sred);
+  if (threadIdx.x == 0) {
+    mnlg_part(w, s, 0)[blockIdx.x] = rz;
+    mnlg_part(w, s, 1)[blockIdx.x] = zz;
+  }
+}
+
+// p = z + beta p
+__global__ __launch_bounds__(MICRO_TPB) void k_mnlg_pupdate(MicroNlArgs a, MnlGridWs w) {
+  const int s = blockIdx.y;
+  if (w.st[s].stage != MNLG_CG) return;
+  const int64_t ndof = 3 * (int64_t)a.m.n * a.m.n * a.m.n, d = (int64_t)blockIdx.x * MICRO_TPB + threadIdx.x;
+  if (d >= ndof) return;
+  double* const sp = mnlg_vec(w, s, 3, ndof);
+  sp[d] = mnlg_vec(w, s, 5, ndof)[d] * mnlg_vec(w, s, 2, ndof)[d] + w.st[s].beta * sp[d];
+}
+
 // One 3x3 block A(node g, node g+d) of the assembled matrix (MatSetValuesLocal(ADD) +
 // MatAssembly + MatZeroRowsColumns(diag = 1), src/assembly.c:106-112, src/bcs.c:341-347):
 // 0 + Ke_e1 + Ke_e2 + ... over the shared elements in ascending element order (the reference's
@@ -7057,6 +7534,57 @@ void launch_mnl_solve(Ctx& c, const MicroNlArgs& a, int nsolve) {
     hipLaunchKernelGGL(k_mnl_solve<false>, dim3(nsolve), dim3(MICRO_TPB), 0, c.stream, a, ngp, c.mnl_list, c.mnl_slot,
                        c.eps, c.sig, c.ctan, c.ftrial, c.mnl_pool, c.mnl_its, c.mnl_rn, c.mnl_cnt, nsolve,
                        (double*)nullptr);
+}
+
+MnlGridWs mnlg_layout(double* base, int n, int64_t batch) {
+  const int64_t ndof = 3 * (int64_t)n * n * n;
+  MnlGridWs w{};
+  w.vec = base;
+  w.npart = (int)mg_npart(n);
+  w.part = w.vec + batch * MNLG_NVEC * ndof;
+  w.st = reinterpret_cast<MnlGridState*>(w.part + batch * MNLG_NPART * w.npart);
+  w.ntile = mg_ntile(n);
+  return w;
+}
+
+void launch_mnlg_start(Ctx& c, const MnlGridWs& w, int base, int cnt) {
+  hipLaunchKernelGGL(k_mnlg_start, dim3((cnt + 63) / 64), dim3(64), 0, c.stream, w, c.mnl_list, c.mnl_slot, base, cnt);
+}
+
+// nine launches: u / x | state or column stresses | D | r, p | Newton control or column | x of the next
+// column | its stresses | r, p | norm0.  The first five serve solves whose CG has ended (or that have
+// just been listed), the last four those the fifth sent into a tangent solve.
+void launch_mnlg_transition(Ctx& c, const MicroNlArgs& a, const MnlGridWs& w, int cnt) {
+  const int64_t ngp = 8 * c.g.nelem;
+  const int nn = a.m.n * a.m.n * a.m.n, nt = w.ntile * w.ntile * w.ntile, nnb = (nn + MICRO_TPB - 1) / MICRO_TPB;
+  const dim3 tiles(nt, cnt), nodes(nnb, cnt), one(cnt), tpb(MICRO_TPB);
+  hipLaunchKernelGGL(k_mnlg_prep<false>, nodes, tpb, 0, c.stream, a, w, ngp, c.eps);
+  hipLaunchKernelGGL(k_mnlg_gp<1>, tiles, tpb, 0, c.stream, a, w, c.mnl_pool);
+  hipLaunchKernelGGL(k_mnlg_diag, nodes, tpb, 0, c.stream, a, w, c.mnl_pool);
+  hipLaunchKernelGGL(k_mnlg_gather<true>, tiles, tpb, 0, c.stream, a, w, c.mnl_pool);
+  hipLaunchKernelGGL(k_mnlg_scalar<0>, one, tpb, 0, c.stream, a, w, nt, ngp, c.sig, c.ctan, c.ftrial, c.mnl_its, c.mnl_rn,
+                     c.mnl_cnt);
+  hipLaunchKernelGGL(k_mnlg_prep<true>, nodes, tpb, 0, c.stream, a, w, ngp, c.eps);
+  hipLaunchKernelGGL(k_mnlg_gp<2>, tiles, tpb, 0, c.stream, a, w, c.mnl_pool);
+  hipLaunchKernelGGL(k_mnlg_gather<true>, tiles, tpb, 0, c.stream, a, w, c.mnl_pool);
+  hipLaunchKernelGGL(k_mnlg_scalar<3>, one, tpb, 0, c.stream, a, w, nt, ngp, c.sig, c.ctan, c.ftrial, c.mnl_its, c.mnl_rn,
+                     c.mnl_cnt);
+}
+
+// six launches: stresses of p | q = K_T p, p.q | pq, alpha | x, r, z | its, rel, beta | p
+void launch_mnlg_iterate(Ctx& c, const MicroNlArgs& a, const MnlGridWs& w, int cnt) {
+  const int64_t ngp = 8 * c.g.nelem;
+  const int nt = w.ntile * w.ntile * w.ntile;
+  const int nvb = (int)((3 * (int64_t)a.m.n * a.m.n * a.m.n + MICRO_TPB - 1) / MICRO_TPB);
+  const dim3 tiles(nt, cnt), dofs(nvb, cnt), one(cnt), tpb(MICRO_TPB);
+  hipLaunchKernelGGL(k_mnlg_gp<0>, tiles, tpb, 0, c.stream, a, w, c.mnl_pool);
+  hipLaunchKernelGGL(k_mnlg_gather<false>, tiles, tpb, 0, c.stream, a, w, c.mnl_pool);
+  hipLaunchKernelGGL(k_mnlg_scalar<1>, one, tpb, 0, c.stream, a, w, nt, ngp, c.sig, c.ctan, c.ftrial, c.mnl_its, c.mnl_rn,
+                     c.mnl_cnt);
+  hipLaunchKernelGGL(k_mnlg_update, dofs, tpb, 0, c.stream, a, w);
+  hipLaunchKernelGGL(k_mnlg_scalar<2>, one, tpb, 0, c.stream, a, w, nvb, ngp, c.sig, c.ctan, c.ftrial, c.mnl_its, c.mnl_rn,
+                     c.mnl_cnt);
+  hipLaunchKernelGGL(k_mnlg_pupdate, dofs, tpb, 0, c.stream, a, w);
 }
 
 void launch_mnl_commit(Ctx& c, const MicroNlArgs& a) {

@@ -64,6 +64,8 @@ constexpr int MICRO_NMAX_DEV = 20;  // ... with the vectors in device memory (mi
                                     // per cell still, and the phase bytes (19^3) stay in LDS
 constexpr int MICRO_NMAX_GRID = 128;  // ... with the grid-wide solver (option micro_solver 1): one
                                       // workgroup per 8x8x8-node tile of a load case, -mat_law micro only
+constexpr int MICRO_NMAX_NL_GRID = 64;  // ... of -mat_law micro_nl with its grid-wide solver (option micro_nl_solver 1,
+                                        // DESIGN §18): a history slot is 224 B x 8 (n-1)^3, 448 MB at n = 64
 constexpr int MICRO_DOFS = 3 * MICRO_NMAX * MICRO_NMAX * MICRO_NMAX;  // LDS vectors are sized for it
 constexpr int MICRO_TPB = 512;
 constexpr int MICRO_OUT = 16;  // doubles a load case leaves: 6 average stresses, iterations, relative norm, converged
@@ -123,6 +125,37 @@ struct MicroNlArgs {
   double nl_rtol;       // Newton: |D^-1 R| <= nl_rtol |D^-1 R_0|
   int nl_max_it;
 };
+
+// option micro_nl_solver 1: the listed points' Newton / CG solves spread over the device,
+// one workgroup per tile of MG_T^3 nodes (or elements) of one solve and one kernel launch per phase;
+// up to `batch` solves share a launch (blockIdx.y).  One allocation holds, in this order: the solves'
+// six vectors ([batch][6][3 n^3]: u, x, r, p, q, D^-1), the partial sums ([batch][MNLG_NPART][npart])
+// and the state records.  A record's stage gates every kernel: the scalar kernels alone write it.
+constexpr int MNLG_NVEC = 6;
+constexpr int MNLG_NPART = 9;  // 0, 1: the dot products; 2 .. 7: the stress sums; 8: the largest trial f
+enum { MNLG_CG = 0, MNLG_TRANS = 1, MNLG_TSTART = 2, MNLG_DONE = 3 };
+struct MnlGridState {
+  double rz, pq, alpha, beta, norm0;  // the running CG
+  double nnorm0, nrel;                // Newton: the first norm, the last relative one
+  double col[36];                     // the tangent's columns as they arrive
+  int64_t q;                          // the macro Gauss point
+  int slot;
+  int stage;   // MNLG_CG: a CG runs; MNLG_TRANS: the next transition starts a Newton step or ends a column;
+               // MNLG_TSTART: (inside a transition) the tangent solve of column lc starts; MNLG_DONE
+  int lc;      // -1: Newton; 0 .. 5: the tangent's column
+  int fresh;   // no state pass yet: u takes its boundary values, D is built
+  int nits, cgits, its, status;  // Newton steps, CG iterations (all, the running CG), 0 ok / 1 Newton / 2 CG
+};
+struct MnlGridWs {
+  double* vec;
+  double* part;
+  MnlGridState* st;
+  int ntile, npart;
+};
+inline int64_t mnlg_ws_bytes(int n, int64_t batch) {
+  const int64_t ndof = 3 * (int64_t)n * n * n;
+  return batch * ((int64_t)sizeof(double) * (MNLG_NVEC * ndof + MNLG_NPART * mg_npart(n)) + (int64_t)sizeof(MnlGridState));
+}
 
 // -pc_type mg: geometric multigrid preconditioner of the macro CG, one rank.  Level 0
 // is the assembled matrix (launch_spmv, whatever its storage); a coarser level keeps its Galerkin
@@ -509,7 +542,8 @@ struct Ctx {
   // where its vectors live), 1 the grid-wide solver (-mat_law micro only, micro_n <= MICRO_NMAX_GRID);
   // micro_grid_poll = CG iterations enqueued between two host polls of the six done flags
   int micro_solver = 0, micro_grid_poll = 16;
-  double* micro_grid_ws = nullptr;  // mg_ws_bytes(n), allocated at the solver's first use
+  double* micro_grid_ws = nullptr;  // mg_ws_bytes(n), allocated at the solver's first use; under micro_nl_solver 1
+                                    // the larger of that and mnlg_ws_bytes: the two solvers never run together
   int64_t micro_grid_bytes = 0;
 
   // -mat_law micro_nl: phase Sy / Ka and the Newton settings; the unit-strain fields' strain
@@ -519,6 +553,10 @@ struct Ctx {
   double mnl_Sy[2] = {}, mnl_Ka[2] = {};
   double mnl_rtol = 1e-10;
   int mnl_max_it = 20;
+  // option micro_nl_solver: 0 k_mnl_solve (one workgroup per listed point), 1 the grid-wide
+  // solver: C_hom by the k_mg_* sequence, the listed points by the k_mnlg_* launches, micro_n <=
+  // MICRO_NMAX_NL_GRID; micro_mem is ignored, micro_mem_blocks > 0 replaces the solves per launch
+  int mnl_solver = 0;
   int64_t mnl_slots_opt = 0;     // option micro_nl_slots (0: what fits 2 GiB, at most the local Gauss points)
   int64_t mnl_cap = 0, mnl_used = 0;
   double* mnl_ufield = nullptr;  // [6][3 n^3] unit-strain solutions
@@ -618,6 +656,11 @@ void launch_mg_finish(Ctx& c, const MicroArgs& m, const MicroGridWs& w);  // ave
 void launch_mnl_conc(Ctx& c, const MicroNlArgs& a);    // mnl_ufield -> mnl_conc
 void launch_mnl_linear(Ctx& c, const MicroNlArgs& a);  // linear test, sigma = C_hom eps, compaction -> mnl_cnt
 void launch_mnl_solve(Ctx& c, const MicroNlArgs& a, int nsolve);
+// option micro_nl_solver 1: the listed points base .. base + cnt - 1, grid-wide
+MnlGridWs mnlg_layout(double* base, int n, int64_t batch);
+void launch_mnlg_start(Ctx& c, const MnlGridWs& w, int base, int cnt);
+void launch_mnlg_transition(Ctx& c, const MicroNlArgs& a, const MnlGridWs& w, int cnt);  // CG ended -> next CG started
+void launch_mnlg_iterate(Ctx& c, const MicroNlArgs& a, const MnlGridWs& w, int cnt);     // one gated CG iteration
 void launch_mnl_commit(Ctx& c, const MicroNlArgs& a);  // new history -> committed history, used slots
 void launch_gather_matrix(Ctx& c);
 void launch_gather_matrix_sym(Ctx& c);

@@ -142,10 +142,12 @@ static int run(int argc, char** argv) {
   /* the flags without an mcx_opts field (-micro_mem, -micro_rtol, -micro_nl_slots, ...) */
   CHK(mcx_apply_args(ctx, argc - 1, (const char* const*)argv + 1));
   const char* micro_mem = "lds";
-  int micro_grid = 0; /* -micro_solver grid */
+  int micro_grid = 0;    /* -micro_solver grid */
+  int micro_nl_grid = 0; /* -micro_nl_solver grid */
   for (int a = 1; a + 1 < argc; a++) {
     if (!strcmp(argv[a], "-micro_mem")) micro_mem = argv[a + 1];
     if (!strcmp(argv[a], "-micro_solver")) micro_grid = !strcmp(argv[a + 1], "grid");
+    if (!strcmp(argv[a], "-micro_nl_solver")) micro_nl_grid = !strcmp(argv[a + 1], "grid");
   }
   mcx_info in;
   CHK(mcx_get_info(ctx, &in));
@@ -190,8 +192,8 @@ static int run(int argc, char** argv) {
       PRINTF("id 0 : E = %e\tnu = %e\n", o.micro_mat_1[0], o.micro_mat_1[1]);
       PRINTF("id 1 : E = %e\tnu = %e\n", o.micro_mat_2[0], o.micro_mat_2[1]);
     }
-    PRINTF("Micro cell : type = %d (%s)\tn = %d\tmem = %s%s\n", o.micro_type, o.micro_type == 0 ? "sphere" : "layer",
-           o.micro_n, micro_mem, micro_grid ? "\tsolver = grid" : "");
+    PRINTF("Micro cell : type = %d (%s)\tn = %d\tmem = %s%s%s\n", o.micro_type, o.micro_type == 0 ? "sphere" : "layer",
+           o.micro_n, micro_mem, micro_grid ? "\tsolver = grid" : "", nl && micro_nl_grid ? "\tnl_solver = grid" : "");
     PRINTF("C_hom : \n");
     for (int k = 0; k < 6; k++)
       PRINTF("%e\t%e\t%e\t%e\t%e\t%e\n", chom[k * 6], chom[k * 6 + 1], chom[k * 6 + 2], chom[k * 6 + 3],
