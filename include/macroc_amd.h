@@ -353,13 +353,26 @@ int mcx_micro_get_phase(void* ctx, unsigned char* phase, int64_t* n);
  * agree with solver 0 to the Newton / CG tolerances, not bit for bit, and are a function of the
  * strain and the committed history alone.  "micro_mem" is ignored under solver 1;
  * "micro_grid_poll" sets the CG iterations enqueued between two host reads of the solves' states.
- * The value changes only while no history slot is in use; other laws accept it without effect. */
+ * The value changes only while no history slot is in use; other laws accept it without effect.
+ * "micro_nl_start" (-micro_nl_start zero|elastic, 0 | 1; default 0) and "micro_nl_ls" (-micro_nl_ls K,
+ * an integer 0 .. 16; default 0) globalise the Newton loop of both solvers.  Start 1: after the first
+ * state pass at the zero interior (D and the first norm are the same bits as under 0) the interior
+ * takes the elastic predictor sum_l eps_l w_l (the six unit-strain fields, ascending l) and the
+ * state is evaluated there; a point that meets the stop then ends with 0 Newton iterations.  K > 0:
+ * after a step's CG the lengths 2^-j, j = 0 .. K, are tried in turn; trial j is accepted when
+ * |D^-1 R_i| at u + 2^-j dx is smaller than at the last accepted iterate, trial K regardless.
+ * Both may change at any time, leave micro_n = 2 as it is and are accepted without effect by other
+ * laws; the defaults keep every bit. */
 /* per Gauss point (mcx_get_gp_strain's order): path 0 = linear shortcut, 1 = solved; Newton
    iterations, CG iterations (Newton steps and tangent solves together) and the final relative
    Newton residual of the last mcx_homogenize.  Any pointer may be NULL. */
 int mcx_micro_nl_get_info(void* ctx, int* path, int* newton_its, int* cg_its, double* rnorm);
 /* slots in use, slots allocated (0 before the first non-linear point) and the bytes of one slot */
 int mcx_micro_nl_get_pool(void* ctx, int64_t* slots_used, int64_t* slots_allocated, int64_t* bytes_per_slot);
+/* per Gauss point (the same order), of the last mcx_homogenize: the rejected step-length trials
+   ("micro_nl_ls") and the smallest accepted length.  A solved point that never backtracked: 0 and
+   1.0; a point on the linear shortcut: 0 and 0.0.  Either pointer may be NULL. */
+int mcx_micro_nl_get_steps(void* ctx, int* ls_rejects, double* min_step);
 
 double mcx_get_displacement(void* ctx, int time_s);
 int mcx_zero_u(void* ctx);                 /* VecZeroEntries(u)  src/init.c:103 */
@@ -426,16 +439,17 @@ int mcx_set_timing(void* ctx, int on);
 int mcx_get_timing(void* ctx, mcx_timing* t);
 int mcx_synchronize(void* ctx);
 /* tuning knobs ("spmv_subl": lines per sub-slab of the SpMV sweep, 0 = whole XCD slab; "micro_rtol",
-   "micro_max_it", "micro_mem", "micro_solver", "micro_grid_poll": the micro cell's CG, -mat_law micro; "micro_nl_rtol", "micro_nl_max_it", "micro_nl_slots", "micro_nl_solver":
+   "micro_max_it", "micro_mem", "micro_solver", "micro_grid_poll": the micro cell's CG, -mat_law micro; "micro_nl_rtol", "micro_nl_max_it", "micro_nl_slots", "micro_nl_solver", "micro_nl_start", "micro_nl_ls":
    -mat_law micro_nl) and a
    device-only SpMV timer (iters launches on the current search direction, HIP events) */
 int mcx_set_option(void* ctx, const char* name, double value);
 /* the command-line flags that have no mcx_opts field, applied to a context through mcx_set_option:
    -micro_mem lds|device ("micro_mem" 0 | 1), -micro_solver cell|grid ("micro_solver" 0 | 1), -micro_nl_solver cell|grid ("micro_nl_solver" 0 | 1),
+   -micro_nl_start zero|elastic ("micro_nl_start" 0 | 1), -micro_nl_ls K ("micro_nl_ls", an integer 0 .. 16),
    -micro_rtol, -micro_max_it, -micro_nl_rtol, -micro_nl_max_it, -micro_nl_slots (each with a
    number), -pc_type jacobi|mg ("pc_type" 0 | 1), -pc_mg_levels N, -mg_levels_ksp_max_it k
    ("pc_mg_smooth"), -pc_mg_dist 0|1 ("pc_mg_dist"; give it before -pc_type), -pc_mg_precision
-   double|single ("pc_mg_precision" 0 | 1).  mcx_parse_args accepts these flags and checks -micro_mem's, -micro_solver's, -micro_nl_solver's and -pc_mg_precision's word; call this after mcx_init with the same argv.  Other flags are skipped. */
+   double|single ("pc_mg_precision" 0 | 1).  mcx_parse_args accepts these flags and checks -micro_mem's, -micro_solver's, -micro_nl_solver's, -micro_nl_start's, -micro_nl_ls's and -pc_mg_precision's word; call this after mcx_init with the same argv.  Other flags are skipped. */
 int mcx_apply_args(void* ctx, int argc, const char* const* argv);
 int mcx_time_spmv(void* ctx, int iters, double* avg_ms);
 

@@ -41,7 +41,7 @@ EXPORTS = [
     "mcx_set_timing", "mcx_get_timing", "mcx_synchronize", "mcx_set_option", "mcx_time_spmv",
     "mcx_set_micropp", "mcx_set_device_law", "mcx_set_gp_stress", "mcx_set_gp_ctan", "mcx_get_gp_strain",
     "mcx_micro_get_ctan", "mcx_micro_get_phase",
-    "mcx_get_gp_ctan", "mcx_micro_nl_get_info", "mcx_micro_nl_get_pool", "mcx_apply_args",
+    "mcx_get_gp_ctan", "mcx_micro_nl_get_info", "mcx_micro_nl_get_pool", "mcx_micro_nl_get_steps", "mcx_apply_args",
     "mcx_pc_apply", "mcx_pc_mg_info", "mcx_pc_mg_dump_csr", "mcx_get_st_dma", "mcx_pc_mg_plan", "mcx_pc_mg_box",
     "mcx_pc_mg_get_precision",
 ]
@@ -191,6 +191,7 @@ def lib():
     ip = C.POINTER(C.c_int)
     L.mcx_micro_nl_get_info.argtypes = [vp, ip, ip, ip, d]
     L.mcx_micro_nl_get_pool.argtypes = [vp, i64, i64, i64]
+    L.mcx_micro_nl_get_steps.argtypes = [vp, ip, d]
     for fn in ("mcx_set_gp_stress", "mcx_set_gp_ctan", "mcx_get_gp_strain", "mcx_get_gp_ctan"):
         getattr(L, fn).argtypes = [vp, d]
     L.mcx_micro_get_ctan.argtypes = [vp, d, C.POINTER(C.c_int), d]
@@ -487,6 +488,15 @@ class Macroc:
                "mcx_micro_nl_get_pool")
         return {"path": path, "newton_its": nit, "cg_its": cg, "rnorm": rn, "slots_used": used.value,
                 "slots": cap.value, "bytes_per_slot": per.value}
+
+    def micro_nl_steps(self):
+        """per Gauss point (gpi order), of the last homogenize: the rejected step-length trials of
+        option micro_nl_ls and the smallest accepted length (a solved point that never backtracked:
+        0 and 1.0; a point on the linear shortcut: 0 and 0.0)."""
+        rej, ms = np.zeros(self.ngp, np.int32), np.zeros(self.ngp)
+        _check(lib().mcx_micro_nl_get_steps(self._ctx, rej.ctypes.data_as(C.POINTER(C.c_int)), _dp(ms)),
+               "mcx_micro_nl_get_steps")
+        return {"ls_rejects": rej, "min_step": ms}
 
     # ---- the micro-scale cell (-mat_law micro)
     def micro_ctan(self):

@@ -258,7 +258,7 @@ static int init_ctx(Ctx& c, const mcx_opts* o, int rank, int nranks, const void*
     const int64_t ngp = 8 * E;
     if ((rc = dalloc(c, &c.ftrial, ngp)) || (rc = dalloc(c, &c.mnl_slot, ngp)) ||
         (rc = dalloc(c, &c.mnl_list, ngp)) || (rc = dalloc(c, &c.mnl_cnt, 4)) ||
-        (rc = dalloc(c, &c.mnl_its, 3 * ngp)) || (rc = dalloc(c, &c.mnl_rn, ngp)))
+        (rc = dalloc(c, &c.mnl_its, 4 * ngp)) || (rc = dalloc(c, &c.mnl_rn, 2 * ngp)))
       return rc;
     MCX_HIP(hipMemsetAsync(c.mnl_slot, 0xff, sizeof(int) * (ngp > 0 ? ngp : 1), c.stream));  // -1: no slot
     c.mnl_Sy[0] = o->micro_mat_1[2];
@@ -399,13 +399,21 @@ using namespace mcx;
 // mcx_opts fields: mcx_parse_args accepts them, mcx_apply_args applies them after mcx_init
 static const char* const kApplyFlags[] = {"-micro_mem",     "-micro_rtol",      "-micro_max_it",  "-micro_nl_rtol",
                                           "-micro_nl_max_it", "-micro_nl_slots", "-micro_solver",
-                                          "-micro_nl_solver",
+                                          "-micro_nl_solver", "-micro_nl_start",  "-micro_nl_ls",
                                           "-pc_type",       "-pc_mg_levels",    "-mg_levels_ksp_max_it",
                                           "-pc_mg_dist",    "-pc_mg_precision"};
 static bool apply_flag(const char* k) {
   for (const char* f : kApplyFlags)
     if (!std::strcmp(k, f)) return true;
   return false;
+}
+
+// -micro_nl_ls K: the word is an integer 0 .. 16
+static bool micro_nl_ls_word(const char* v) {
+  if (!v || !*v) return false;
+  char* end = nullptr;
+  const long k = std::strtol(v, &end, 10);
+  return !*end && k >= 0 && k <= 16;
 }
 
 #define CTX(p) Ctx& c = *reinterpret_cast<Ctx*>(p)
@@ -537,6 +545,14 @@ int mcx_parse_args(mcx_opts* o, int argc, const char* const* argv) try {
       }
       if (!std::strcmp(k, "-micro_nl_solver") && (!v || (std::strcmp(v, "cell") && std::strcmp(v, "grid")))) {
         set_error(std::string("-micro_nl_solver: cell or grid, got ") + (v ? v : "(none)"));
+        return 2;
+      }
+      if (!std::strcmp(k, "-micro_nl_start") && (!v || (std::strcmp(v, "zero") && std::strcmp(v, "elastic")))) {
+        set_error(std::string("-micro_nl_start: zero or elastic, got ") + (v ? v : "(none)"));
+        return 2;
+      }
+      if (!std::strcmp(k, "-micro_nl_ls") && !micro_nl_ls_word(v)) {
+        set_error(std::string("-micro_nl_ls: an integer 0 .. 16, got ") + (v ? v : "(none)"));
         return 2;
       }
       if (!std::strcmp(k, "-pc_mg_precision") && (!v || (std::strcmp(v, "double") && std::strcmp(v, "single")))) {
@@ -866,6 +882,8 @@ static MicroNlArgs mnl_args(const Ctx& c) {
   }
   a.nl_rtol = c.mnl_rtol;
   a.nl_max_it = c.mnl_max_it;
+  a.nl_start = c.mnl_start;
+  a.nl_ls = c.mnl_ls;
   return a;
 }
 
@@ -1027,25 +1045,37 @@ static int64_t mnl_slot_bytes(const Ctx& c) {
 // iterations, then reads the records back; the device steps every solve through k_mnl_solve's
 // loop by itself and counts its own iterations, so what is enqueued for a solve in another stage
 // changes nothing and the results do not depend on micro_grid_poll or on the batch.
+// With micro_nl_start 1 or micro_nl_ls > 0 a transition may leave a solve before
+// another state pass (the predictor, a rejected trial).  A round whose read-back (or start) shows a
+// solve about to take a Newton state pass therefore holds a second transition, which makes that
+// pass, so that the solve does not idle through the round's CG iterations; other rounds hold one.
 static int solve_mnl_grid(Ctx& c, const MicroNlArgs& a, int nsolve) {
   const int64_t batch = mnl_grid_batch(c);
   if (int rc = micro_resize(c, &c.micro_grid_ws, &c.micro_grid_bytes, grid_ws_bytes(c))) return rc;
   const MnlGridWs w = mnlg_layout(c.micro_grid_ws, a.m.n, batch);
   const int per = std::max(1, std::min(c.micro_grid_poll, a.m.max_it));
   // a solve has at most nl_max_it + 1 state passes and six columns, each CG at most max_it iterations
-  const int64_t max_rounds = (int64_t)(a.nl_max_it + 8) * ((int64_t)(std::max(a.m.max_it, 1) + per - 1) / per + 1);
+  // (and, globalised, one more pass for the predictor and up to nl_ls more per step)
+  const int64_t max_rounds = (int64_t)((a.nl_max_it + 1) * (a.nl_ls + 1) + 8) * ((int64_t)(std::max(a.m.max_it, 1) + per - 1) / per + 1);
+  const bool globalised = a.nl_start || a.nl_ls > 0;
   std::vector<MnlGridState> h((size_t)batch);
   for (int base = 0; base < nsolve; base += (int)batch) {
     const int cnt = (int)std::min<int64_t>(batch, nsolve - base);
     launch_mnlg_start(c, w, base, cnt);
+    bool newton_pass = true;  // a solve of the batch is at a Newton state pass (all are, at the start)
     for (int64_t round = 0;; round++) {
       launch_mnlg_transition(c, a, w, cnt);
+      if (globalised && newton_pass) launch_mnlg_transition(c, a, w, cnt);
       for (int q = 0; q < per; q++) launch_mnlg_iterate(c, a, w, cnt);
       MCX_HIP(hipGetLastError());
       MCX_HIP(hipMemcpyAsync(h.data(), w.st, sizeof(MnlGridState) * cnt, hipMemcpyDeviceToHost, c.stream));
       MCX_HIP(hipStreamSynchronize(c.stream));
       bool done = true;
-      for (int s = 0; s < cnt; s++) done = done && h[s].stage == MNLG_DONE;
+      newton_pass = false;
+      for (int s = 0; s < cnt; s++) {
+        done = done && h[s].stage == MNLG_DONE;
+        newton_pass = newton_pass || (h[s].stage == MNLG_TRANS && h[s].lc < 0);
+      }
       if (done) break;
       if (round >= max_rounds) {
         set_error("-mat_law micro_nl: micro_nl_solver 1 did not end within its iteration limits (internal error)");
@@ -1116,22 +1146,26 @@ static int micro_nl_homogenize(Ctx& c) {
   MCX_HIP(hipMemcpyAsync(h, c.mnl_cnt, sizeof(h), hipMemcpyDeviceToHost, c.stream));
   MCX_HIP(hipStreamSynchronize(c.stream));
   if (h[2] > 0) {  // nothing unconverged is used: name the count and the worst point
-    std::vector<int> its((size_t)3 * ngp);
-    std::vector<double> rn((size_t)ngp);
+    std::vector<int> its((size_t)4 * ngp);
+    std::vector<double> rn((size_t)2 * ngp);
     MCX_HIP(hipMemcpy(its.data(), c.mnl_its, sizeof(int) * its.size(), hipMemcpyDeviceToHost));
     MCX_HIP(hipMemcpy(rn.data(), c.mnl_rn, sizeof(double) * rn.size(), hipMemcpyDeviceToHost));
     int64_t worst = -1;
     for (int64_t q = 0; q < ngp; q++)
       if (its[2 * ngp + q] && (worst < 0 || !(rn[q] <= rn[worst]))) worst = q;
     const int64_t E = c.g.nelem;
-    char buf[400];
-    std::snprintf(buf, sizeof(buf),
+    char buf[520];
+    int len = std::snprintf(buf, sizeof(buf),
                   "-mat_law micro_nl: %d of %d micro cells did not converge; worst: Gauss point %lld (%s): %d Newton "
                   "iterations (micro_nl_max_it %d), %d CG iterations (micro_max_it %d), relative residual %.3e > "
                   "micro_nl_rtol %.3e",
                   h[2], h[1], (long long)((worst % E) * 8 + worst / E),
                   its[2 * ngp + worst] == 1 ? "Newton gave up" : "the inner CG did not converge", its[worst],
                   a.nl_max_it, its[ngp + worst], a.m.max_it, rn[worst], a.nl_rtol);
+    if (a.nl_start || a.nl_ls > 0)
+      std::snprintf(buf + len, sizeof(buf) - (size_t)len,
+                    " (micro_nl_start %d, micro_nl_ls %d: %d rejected trials, smallest accepted step %g)", a.nl_start,
+                    a.nl_ls, its[3 * ngp + worst], rn[ngp + worst]);
     set_error(buf);
     return 35;
   }
@@ -1317,6 +1351,26 @@ int mcx_micro_nl_get_info(void* ctx, int* path, int* newton_its, int* cg_its, do
       if (newton_its) newton_its[i] = its[q];
       if (cg_its) cg_its[i] = its[ngp + q];
       if (rnorm) rnorm[i] = rn[q];
+    }
+  return 0;
+} MCX_CATCH
+
+int mcx_micro_nl_get_steps(void* ctx, int* ls_rejects, double* min_step) try {
+  MCX_ENTRY();
+  GUARD(ctx);
+  CTX(ctx);
+  if (int rc = need_micro_nl(c, "mcx_micro_nl_get_steps")) return rc;
+  const int64_t E = c.g.nelem, ngp = 8 * E;
+  std::vector<int> rej((size_t)ngp);
+  std::vector<double> ms((size_t)ngp);
+  MCX_HIP(hipMemcpyAsync(rej.data(), c.mnl_its + 3 * ngp, sizeof(int) * rej.size(), hipMemcpyDeviceToHost, c.stream));
+  MCX_HIP(hipMemcpyAsync(ms.data(), c.mnl_rn + ngp, sizeof(double) * ms.size(), hipMemcpyDeviceToHost, c.stream));
+  MCX_HIP(hipStreamSynchronize(c.stream));
+  for (int64_t e = 0; e < E; e++)
+    for (int gp = 0; gp < 8; gp++) {
+      const int64_t q = gp * E + e, i = e * 8 + gp;
+      if (ls_rejects) ls_rejects[i] = rej[q];
+      if (min_step) min_step[i] = ms[q];
     }
   return 0;
 } MCX_CATCH
@@ -2212,6 +2266,22 @@ int mcx_set_option(void* ctx, const char* name, double value) try {
     c.mnl_max_it = (int)value;
     return 0;
   }
+  if (!std::strcmp(name, "micro_nl_start")) {  // the cell's first Newton iterate; other laws: no effect
+    if (value != 0. && value != 1.) {
+      set_error("micro_nl_start: 0 (zero: the boundary values, 0 inside) or 1 (elastic: the superposed unit-strain fields inside)");
+      return 1;
+    }
+    c.mnl_start = (int)value;
+    return 0;
+  }
+  if (!std::strcmp(name, "micro_nl_ls")) {  // the Newton step's lengths 2^-j, j = 0 .. K; 0: full steps
+    if (!(value >= 0. && value <= 16.) || value != (double)(int)value) {
+      set_error("micro_nl_ls: an integer 0 (full Newton steps) .. 16 (step lengths down to 2^-16)");
+      return 1;
+    }
+    c.mnl_ls = (int)value;
+    return 0;
+  }
   if (!std::strcmp(name, "micro_nl_slots")) {  // 0: what fits 2 GiB, at most the local Gauss points
     if (!(value >= 0.)) {
       set_error("micro_nl_slots: >= 0");
@@ -2765,6 +2835,18 @@ int mcx_apply_args(void* ctx, int argc, const char* const* argv) try {
         return 2;
       }
       value = std::strcmp(v, "grid") ? 0. : 1.;
+    } else if (!std::strcmp(k, "-micro_nl_start")) {
+      if (std::strcmp(v, "zero") && std::strcmp(v, "elastic")) {
+        set_error(std::string("-micro_nl_start: zero or elastic, got ") + v);
+        return 2;
+      }
+      value = std::strcmp(v, "elastic") ? 0. : 1.;
+    } else if (!std::strcmp(k, "-micro_nl_ls")) {
+      if (!micro_nl_ls_word(v)) {
+        set_error(std::string("-micro_nl_ls: an integer 0 .. 16, got ") + v);
+        return 2;
+      }
+      value = std::atof(v);
     } else if (!std::strcmp(k, "-pc_mg_precision")) {
       if (std::strcmp(v, "double") && std::strcmp(v, "single")) {
         set_error(std::string("-pc_mg_precision: double or single, got ") + v);

@@ -1039,7 +1039,9 @@ __global__ __launch_bounds__(TPB) void k_mnl_linear(int64_t ngp, Material mat, i
   its[q] = 0;
   its[ngp + q] = 0;
   its[2 * ngp + q] = 0;
+  its[3 * ngp + q] = 0;
   rn[q] = 0.;
+  rn[ngp + q] = 0.;
 }
 
 // ordered compaction by one block: cnt[0] = flagged points; when used + cnt[0] <= cap they get the
@@ -1122,6 +1124,16 @@ __device__ __forceinline__ void mnl_boundary(double* __restrict__ v, int n, cons
 #pragma unroll
     for (int r = 0; r < 3; r++) v[3 * nd + r] = bnd ? Eb[r][0] * X[0] + Eb[r][1] * X[1] + Eb[r][2] * X[2] : 0.;
   }
+}
+
+// option micro_nl_start 1: dof d of the elastic predictor, sum_l eps_l w_l over the six
+// unit-strain fields in ascending l; one statement for every solver form
+__device__ __forceinline__ double mnl_predict(const double* __restrict__ ufield, int64_t ndof, int64_t d,
+                                              const double (&em)[6]) {
+  double s = em[0] * ufield[d];
+#pragma unroll
+  for (int l = 1; l < 6; l++) s = fma(em[l], ufield[(size_t)l * ndof + d], s);
+  return s;
 }
 
 // work stresses of the slot = C_gp B v at every micro Gauss point (the frozen tangents of the slot)
@@ -1226,7 +1238,8 @@ __global__ __launch_bounds__(MICRO_TPB) void k_mnl_solve(MicroNlArgs a, int64_t 
                                                          double* __restrict__ sig, double* __restrict__ ctan,
                                                          double* __restrict__ ftrial, double* __restrict__ pool,
                                                          int* __restrict__ its_out, double* __restrict__ rn_out,
-                                                         int* __restrict__ cnt, int nsolve, double* wsp) {
+                                                         int* __restrict__ cnt, int nsolve, double* wsp,
+                                                         const double* __restrict__ ufield) {
   constexpr int NMAX = DEV ? MICRO_NMAX_DEV : MICRO_NMAX, LV = DEV ? 1 : MICRO_DOFS;
   __shared__ double lu[LV], lx[LV], lr[LV], lp[LV], lq[LV], ld[LV];
   __shared__ double sdn[8 * 24];
@@ -1265,8 +1278,12 @@ __global__ __launch_bounds__(MICRO_TPB) void k_mnl_solve(MicroNlArgs a, int64_t 
     __syncthreads();
 
     // one loop, one CG: Newton steps (lc < 0), then the six frozen-tangent load cases lc = 0..5
-    int lc = -1, nits = 0, cgits = 0, status = 0;
-    double nnorm0 = 0., nrel = 0., fmax = -1e300;
+    // options micro_nl_start / micro_nl_ls: first: no state pass yet; trial: the step
+    // length lam = 2^-trial of the last CG's step (kept in sx) is under test against nacc, the norm
+    // at the last accepted iterate
+    int lc = -1, nits = 0, cgits = 0, status = 0, trial = -1, rejects = 0;
+    bool first = true;
+    double nnorm0 = 0., nrel = 0., fmax = -1e300, nacc = 0., lam = 1., minstep = 1.;
     for (;;) {
       if (lc < 0) {
         // state at the iterate su: stresses, new histories and tangent data of every micro point
@@ -1289,9 +1306,10 @@ __global__ __launch_bounds__(MICRO_TPB) void k_mnl_solve(MicroNlArgs a, int64_t 
 #pragma unroll
           for (int k = 0; k < 6; k++) ws[(size_t)(MNL_SIG + k) * nmgp + mg] = s[k];
         }
-        for (int d = tid; d < ndof; d += MICRO_TPB) sx[d] = 0.;
+        if (trial < 0)
+          for (int d = tid; d < ndof; d += MICRO_TPB) sx[d] = 0.;
         __syncthreads();
-        if (nits == 0) {  // D: the diagonal of K_T at the first iterate, kept for every later solve
+        if (first) {  // D: the diagonal of K_T at the first iterate, kept for every later solve
           for (int nd = tid; nd < nn; nd += MICRO_TPB) {
             const int i = nd % n, j = (nd / n) % n, k = nd / (n * n);
             if (i == 0 || j == 0 || k == 0 || i == ne || j == ne || k == ne) continue;
@@ -1335,7 +1353,36 @@ __global__ __launch_bounds__(MICRO_TPB) void k_mnl_solve(MicroNlArgs a, int64_t 
       micro_reduce2(rz, zz, sred);
       const double norm0 = sqrt(zz);
       if (lc < 0) {
-        if (nits == 0) nnorm0 = norm0;
+        const bool predict = first && a.nl_start;
+        if (first) nnorm0 = norm0;
+        first = false;
+        if (predict && nnorm0 != 0.) {  // the interior takes the elastic predictor; D and nnorm0 stay
+          double em[6];
+#pragma unroll
+          for (int l = 0; l < 6; l++) em[l] = eps[l * ngp + q];
+          for (int nd = tid; nd < nn; nd += MICRO_TPB) {
+            const int i = nd % n, j = (nd / n) % n, k = nd / (n * n);
+            if (i == 0 || j == 0 || k == 0 || i == ne || j == ne || k == ne) continue;
+#pragma unroll
+            for (int r = 0; r < 3; r++) su[3 * nd + r] = mnl_predict(ufield, ndof, 3 * nd + r, em);
+          }
+          __syncthreads();
+          continue;
+        }
+        if (trial >= 0) {
+          if (!(norm0 < nacc) && trial < a.nl_ls) {  // rejected: u = u_accepted + 2^-(trial + 1) dx
+            rejects++;
+            trial++;
+            lam *= 0.5;
+            for (int d = tid; d < ndof; d += MICRO_TPB) su[d] = fma(-lam, sx[d], su[d]);
+            __syncthreads();
+            continue;
+          }
+          minstep = lam < minstep ? lam : minstep;
+          trial = -1;
+          for (int d = tid; d < ndof; d += MICRO_TPB) sx[d] = 0.;  // (read next after the CG's barriers)
+        }
+        nacc = norm0;
         nrel = nnorm0 == 0. ? 0. : norm0 / nnorm0;
         if (nnorm0 == 0. || nrel <= a.nl_rtol) {
           // converged: the volume average of the micro stresses (the cell's volume is 1), then the tangent
@@ -1408,6 +1455,7 @@ __global__ __launch_bounds__(MICRO_TPB) void k_mnl_solve(MicroNlArgs a, int64_t 
       if (lc < 0) {
         for (int d = tid; d < ndof; d += MICRO_TPB) su[d] += sx[d];
         nits++;
+        if (a.nl_ls > 0) trial = 0, lam = 1.;
         __syncthreads();
         continue;
       }
@@ -1433,6 +1481,8 @@ __global__ __launch_bounds__(MICRO_TPB) void k_mnl_solve(MicroNlArgs a, int64_t 
       its_out[ngp + q] = cgits;
       its_out[2 * ngp + q] = status;
       rn_out[q] = nrel;
+      its_out[3 * ngp + q] = rejects;
+      rn_out[ngp + q] = minstep;
       if (status) atomicAdd(cnt + 2, 1);
     }
     if (!DEV) break;
@@ -1825,29 +1875,59 @@ __global__ void k_mnlg_start(MnlGridWs w, const int* __restrict__ list, const in
   st.stage = MNLG_TRANS;
   st.lc = -1;
   st.fresh = 1;
+  st.trial = -1;
+  st.lam = 1.;
+  st.minstep = 1.;
   w.st[s] = st;
 }
 
 // one thread per node.  Newton (TSTART false, a solve in transition with lc < 0): u = Eb x on the
 // boundary, 0 inside and D^-1 = 0 before the first state pass, u += x after a step; x = 0.
-// TSTART: x = E_lc x on the boundary, 0 inside (mnl_boundary's statement in both).
+// Options micro_nl_start / micro_nl_ls, by the record's pend: MNLG_PEND_PRED the
+// interior of u takes the elastic predictor, MNLG_PEND_BACK u -= lam x (a rejected trial's next
+// length); with micro_nl_ls > 0 x keeps the step through its trials.
+// TSTART: x = E_lc x on the boundary, 0 inside (mnl_boundary's statement in both); with
+// micro_nl_ls > 0 also x = 0 for a solve whose Newton CG scalar<0> has just started.
 template <bool TSTART>
 __global__ __launch_bounds__(MICRO_TPB) void k_mnlg_prep(MicroNlArgs a, MnlGridWs w, int64_t ngp,
-                                                         const double* __restrict__ eps) {
+                                                         const double* __restrict__ eps,
+                                                         const double* __restrict__ ufield) {
   const int s = blockIdx.y;
   const MnlGridState& st = w.st[s];
-  if (st.stage != (TSTART ? MNLG_TSTART : MNLG_TRANS) || (!TSTART && st.lc >= 0)) return;
+  const bool xzero = TSTART && a.nl_ls > 0 && st.stage == MNLG_CG && st.lc < 0 && st.its == 0;
+  if (!xzero && (st.stage != (TSTART ? MNLG_TSTART : MNLG_TRANS) || (!TSTART && st.lc >= 0))) return;
   const int n = a.m.n, ne = n - 1, nn = n * n * n, lc = st.lc;
   const int nd = blockIdx.x * MICRO_TPB + threadIdx.x;
   if (nd >= nn) return;
   const int64_t ndof = 3 * (int64_t)nn;
   double* const su = mnlg_vec(w, s, 0, ndof);
   double* const sx = mnlg_vec(w, s, 1, ndof);
+  if (xzero) {
+#pragma unroll
+    for (int r = 0; r < 3; r++) sx[3 * (size_t)nd + r] = 0.;
+    return;
+  }
+  if (!TSTART && st.pend == MNLG_PEND_PRED) {
+    const int i = nd % n, j = (nd / n) % n, k = nd / (n * n);
+    if (i == 0 || j == 0 || k == 0 || i == ne || j == ne || k == ne) return;
+    double em[6];
+#pragma unroll
+    for (int l = 0; l < 6; l++) em[l] = eps[l * ngp + st.q];
+#pragma unroll
+    for (int r = 0; r < 3; r++) su[3 * (size_t)nd + r] = mnl_predict(ufield, ndof, 3 * (int64_t)nd + r, em);
+    return;
+  }
+  if (!TSTART && st.pend == MNLG_PEND_BACK) {
+    const double lam = st.lam;
+#pragma unroll
+    for (int r = 0; r < 3; r++) su[3 * (size_t)nd + r] = fma(-lam, sx[3 * (size_t)nd + r], su[3 * (size_t)nd + r]);
+    return;
+  }
   if (!TSTART && !st.fresh) {
 #pragma unroll
     for (int r = 0; r < 3; r++) {
       su[3 * (size_t)nd + r] += sx[3 * (size_t)nd + r];
-      sx[3 * (size_t)nd + r] = 0.;
+      if (a.nl_ls <= 0) sx[3 * (size_t)nd + r] = 0.;
     }
     return;
   }
@@ -2117,7 +2197,9 @@ __device__ __forceinline__ void mnlg_end(MnlGridState& st, int64_t ngp, int* __r
   its_out[st.q] = st.nits;
   its_out[ngp + st.q] = st.cgits;
   its_out[2 * ngp + st.q] = st.status;
+  its_out[3 * ngp + st.q] = st.rejects;
   rn_out[st.q] = st.nrel;
+  rn_out[ngp + st.q] = st.minstep;
   if (st.status) atomicAdd(cnt + 2, 1);
   st.stage = MNLG_DONE;
 }
@@ -2166,9 +2248,27 @@ __global__ __launch_bounds__(MICRO_TPB) void k_mnlg_scalar(MicroNlArgs a, MnlGri
   if (PHASE == 0) {
     if (st.lc < 0) {
       const double norm0 = sqrt(sb);
-      if (st.nits == 0) st.nnorm0 = norm0;
-      st.nrel = st.nnorm0 == 0. ? 0. : norm0 / st.nnorm0;
+      const bool first = st.fresh != 0;
+      if (first) st.nnorm0 = norm0;
       st.fresh = 0;
+      st.pend = MNLG_PEND_NONE;
+      if (first && a.nl_start && st.nnorm0 != 0.) {  // the next transition's state pass is at the predictor
+        st.pend = MNLG_PEND_PRED;
+        return;
+      }
+      if (st.trial >= 0) {
+        if (!(norm0 < st.nacc) && st.trial < a.nl_ls) {  // rejected: the next transition tries half the length
+          st.rejects++;
+          st.trial++;
+          st.lam *= 0.5;
+          st.pend = MNLG_PEND_BACK;
+          return;
+        }
+        st.minstep = st.lam < st.minstep ? st.lam : st.minstep;
+        st.trial = -1;
+      }
+      st.nacc = norm0;
+      st.nrel = st.nnorm0 == 0. ? 0. : norm0 / st.nnorm0;
       if (st.nnorm0 == 0. || st.nrel <= a.nl_rtol) {
         // converged: the volume average of the micro stresses (the cell's volume is 1), then the tangent
 #pragma unroll
@@ -2214,7 +2314,10 @@ __global__ __launch_bounds__(MICRO_TPB) void k_mnlg_scalar(MicroNlArgs a, MnlGri
     st.its++;
     if (sqrt(sb) / st.norm0 <= a.m.rtol) {
       st.cgits += st.its;
-      if (st.lc < 0) st.nits++;
+      if (st.lc < 0) {
+        st.nits++;
+        if (a.nl_ls > 0) st.trial = 0, st.lam = 1.;
+      }
       st.stage = MNLG_TRANS;
     } else {
       st.beta = sa / st.rz;
@@ -7529,11 +7632,11 @@ void launch_mnl_solve(Ctx& c, const MicroNlArgs& a, int nsolve) {
   if (c.micro_mem)  // at most mnl_ws_blocks workspaces: the blocks walk the list
     hipLaunchKernelGGL(k_mnl_solve<true>, dim3(std::min(nsolve, c.mnl_ws_blocks)), dim3(MICRO_TPB), 0, c.stream, a, ngp,
                        c.mnl_list, c.mnl_slot, c.eps, c.sig, c.ctan, c.ftrial, c.mnl_pool, c.mnl_its, c.mnl_rn,
-                       c.mnl_cnt, nsolve, c.mnl_ws);
+                       c.mnl_cnt, nsolve, c.mnl_ws, c.mnl_ufield);
   else
     hipLaunchKernelGGL(k_mnl_solve<false>, dim3(nsolve), dim3(MICRO_TPB), 0, c.stream, a, ngp, c.mnl_list, c.mnl_slot,
                        c.eps, c.sig, c.ctan, c.ftrial, c.mnl_pool, c.mnl_its, c.mnl_rn, c.mnl_cnt, nsolve,
-                       (double*)nullptr);
+                       (double*)nullptr, c.mnl_ufield);
 }
 
 MnlGridWs mnlg_layout(double* base, int n, int64_t batch) {
@@ -7558,13 +7661,13 @@ void launch_mnlg_transition(Ctx& c, const MicroNlArgs& a, const MnlGridWs& w, in
   const int64_t ngp = 8 * c.g.nelem;
   const int nn = a.m.n * a.m.n * a.m.n, nt = w.ntile * w.ntile * w.ntile, nnb = (nn + MICRO_TPB - 1) / MICRO_TPB;
   const dim3 tiles(nt, cnt), nodes(nnb, cnt), one(cnt), tpb(MICRO_TPB);
-  hipLaunchKernelGGL(k_mnlg_prep<false>, nodes, tpb, 0, c.stream, a, w, ngp, c.eps);
+  hipLaunchKernelGGL(k_mnlg_prep<false>, nodes, tpb, 0, c.stream, a, w, ngp, c.eps, c.mnl_ufield);
   hipLaunchKernelGGL(k_mnlg_gp<1>, tiles, tpb, 0, c.stream, a, w, c.mnl_pool);
   hipLaunchKernelGGL(k_mnlg_diag, nodes, tpb, 0, c.stream, a, w, c.mnl_pool);
   hipLaunchKernelGGL(k_mnlg_gather<true>, tiles, tpb, 0, c.stream, a, w, c.mnl_pool);
   hipLaunchKernelGGL(k_mnlg_scalar<0>, one, tpb, 0, c.stream, a, w, nt, ngp, c.sig, c.ctan, c.ftrial, c.mnl_its, c.mnl_rn,
                      c.mnl_cnt);
-  hipLaunchKernelGGL(k_mnlg_prep<true>, nodes, tpb, 0, c.stream, a, w, ngp, c.eps);
+  hipLaunchKernelGGL(k_mnlg_prep<true>, nodes, tpb, 0, c.stream, a, w, ngp, c.eps, c.mnl_ufield);
   hipLaunchKernelGGL(k_mnlg_gp<2>, tiles, tpb, 0, c.stream, a, w, c.mnl_pool);
   hipLaunchKernelGGL(k_mnlg_gather<true>, tiles, tpb, 0, c.stream, a, w, c.mnl_pool);
   hipLaunchKernelGGL(k_mnlg_scalar<3>, one, tpb, 0, c.stream, a, w, nt, ngp, c.sig, c.ctan, c.ftrial, c.mnl_its, c.mnl_rn,

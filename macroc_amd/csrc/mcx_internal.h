@@ -124,6 +124,7 @@ struct MicroNlArgs {
   double Sy[2], Ka[2];
   double nl_rtol;       // Newton: |D^-1 R| <= nl_rtol |D^-1 R_0|
   int nl_max_it;
+  int nl_start, nl_ls;  // options micro_nl_start, micro_nl_ls: elastic predictor, step lengths 2^-j, j <= nl_ls
 };
 
 // option micro_nl_solver 1: the listed points' Newton / CG solves spread over the device,
@@ -134,6 +135,8 @@ struct MicroNlArgs {
 constexpr int MNLG_NVEC = 6;
 constexpr int MNLG_NPART = 9;  // 0, 1: the dot products; 2 .. 7: the stress sums; 8: the largest trial f
 enum { MNLG_CG = 0, MNLG_TRANS = 1, MNLG_TSTART = 2, MNLG_DONE = 3 };
+// what k_mnlg_prep does to u before a Newton solve's next state pass
+enum { MNLG_PEND_NONE = 0, MNLG_PEND_PRED = 1, MNLG_PEND_BACK = 2 };
 struct MnlGridState {
   double rz, pq, alpha, beta, norm0;  // the running CG
   double nnorm0, nrel;                // Newton: the first norm, the last relative one
@@ -145,6 +148,10 @@ struct MnlGridState {
   int lc;      // -1: Newton; 0 .. 5: the tangent's column
   int fresh;   // no state pass yet: u takes its boundary values, D is built
   int nits, cgits, its, status;  // Newton steps, CG iterations (all, the running CG), 0 ok / 1 Newton / 2 CG
+  // options micro_nl_start / micro_nl_ls
+  int pend;                      // MNLG_PEND_*: the predictor or a shorter trial is owed to u
+  int trial, rejects;            // the trial under test (-1: none; its length is 2^-trial), rejected trials
+  double nacc, lam, minstep;     // the norm at the last accepted iterate, 2^-trial, the smallest accepted length
 };
 struct MnlGridWs {
   double* vec;
@@ -557,6 +564,7 @@ struct Ctx {
   // solver: C_hom by the k_mg_* sequence, the listed points by the k_mnlg_* launches, micro_n <=
   // MICRO_NMAX_NL_GRID; micro_mem is ignored, micro_mem_blocks > 0 replaces the solves per launch
   int mnl_solver = 0;
+  int mnl_start = 0, mnl_ls = 0;  // options micro_nl_start, micro_nl_ls: the globalised Newton loop
   int64_t mnl_slots_opt = 0;     // option micro_nl_slots (0: what fits 2 GiB, at most the local Gauss points)
   int64_t mnl_cap = 0, mnl_used = 0;
   double* mnl_ufield = nullptr;  // [6][3 n^3] unit-strain solutions
@@ -565,8 +573,8 @@ struct Ctx {
   int* mnl_slot = nullptr;       // [ngp]
   int* mnl_list = nullptr;       // [ngp] points to solve, ascending
   int* mnl_cnt = nullptr;        // [2] new points, points to solve
-  int* mnl_its = nullptr;        // [3][ngp] Newton iterations, CG iterations, status (0 ok, 1 Newton, 2 CG)
-  double* mnl_rn = nullptr;      // [ngp] final relative Newton residual
+  int* mnl_its = nullptr;        // [4][ngp] Newton iterations, CG iterations, status (0 ok, 1 Newton, 2 CG), rejected trials
+  double* mnl_rn = nullptr;      // [2][ngp] final relative Newton residual, smallest accepted step length
   double* mnl_pool = nullptr;    // [mnl_cap][MNL_WS][8 (n-1)^3]
 
   // options pc_type (0 Jacobi, 1 multigrid), pc_mg_levels (0: automatic), pc_mg_smooth (Chebyshev degree)

@@ -5,10 +5,15 @@ point) and by solver 1 (grid-wide), and the linear-shortcut test alone on a grid
     python tools/bench_micro_nl_grid.py --n 10 16 20 --solver 0 1 --points 8 256
     python tools/bench_micro_nl_grid.py --n 32 48 64 --solver 1 --points 8 --ka 1e7
     python tools/bench_micro_nl_grid.py --n 33 --solver 1 --points --linear 16
+    python tools/bench_micro_nl_grid.py --n 10 16 --solver 1 --points 8 --start 0 1 --ls 0 5
+    python tools/bench_micro_nl_grid.py --n 17 --solver 1 --seed 5 --amp 2e-3 --stages 1 1.5 --start 1 --ls 5
 
 Sphere cells, the tests' load (seed 5; --amp scales it); --ka sets the matrix' hardening modulus (the
 cells' plain Newton gives up on resolved cells with the tests' 1e6, DESIGN §18).  Host clock between two mcx_synchronize;
 the second call of each is reported (the first one allocates).  One JSON line per measurement.
+--start / --ls list values of the options micro_nl_start / micro_nl_ls, every pair is
+measured in the same process; --stages lists load factors with a commit between them, the last one
+is the one timed.  A stage whose cells do not converge is reported with the message, not raised.
 """
 import argparse
 import json
@@ -35,10 +40,11 @@ def field(grid, seed=5, amp=4e-3, wobble=0.15):
     return (X @ strain_tensor(e0).T + wobble * amp * rng.uniform(-1, 1, X.shape)).ravel()
 
 
-def argv_of(n, grid, ka=MAT1[3]):
+def argv_of(n, grid, ka=MAT1[3], equal=False):
+    mat1 = MAT1[:3] + (ka,)
     return ["-da_grid_x", grid[0], "-da_grid_y", grid[1], "-da_grid_z", grid[2], "-lx", grid[0] - 1, "-ly", grid[1] - 1,
             "-lz", grid[2] - 1, "-mat_law", "micro_nl", "-micro_n", n, "-micro_type", 0,
-            "-micro_mat_1", "%r,%r,%r,%r" % (MAT1[:3] + (ka,)), "-micro_mat_2", "%r,%r,%r,%r" % MAT2]
+            "-micro_mat_1", "%r,%r,%r,%r" % mat1, "-micro_mat_2", "%r,%r,%r,%r" % (mat1 if equal else MAT2)]
 
 
 def timed(m, fn):
@@ -56,6 +62,11 @@ def main():
     ap.add_argument("--points", type=int, nargs="*", default=[8], help="Gauss points, all yielding: " + str(sorted(GRIDS)))
     ap.add_argument("--amp", type=float, default=4e-3, help="amplitude of the load")
     ap.add_argument("--ka", type=float, default=MAT1[3], help="hardening modulus of the matrix phase")
+    ap.add_argument("--equal", action="store_true", help="both phases are the matrix (the cell is the J2 law)")
+    ap.add_argument("--seed", type=int, default=5, help="seed of the load")
+    ap.add_argument("--stages", type=float, nargs="+", default=[1.0], help="load factors, a commit between them; the last is timed")
+    ap.add_argument("--start", type=int, nargs="+", default=[0], help="option micro_nl_start")
+    ap.add_argument("--ls", type=int, nargs="+", default=[0], help="option micro_nl_ls")
     ap.add_argument("--poll", type=int, default=0, help="option micro_grid_poll (0: leave it alone)")
     ap.add_argument("--linear", type=int, default=0, help="nodes per edge of a macro grid below yield: the linear test alone")
     ap.add_argument("--root", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -66,31 +77,51 @@ def main():
 
     for n in a.n:
         for solver in a.solver:
-            for pts in a.points:
+            for pts, start, ls in [(p, s, k) for p in a.points for s in a.start for k in a.ls]:
                 grid = GRIDS[pts]
-                with M.Macroc(argv_of(n, grid, a.ka)) as m:
+                u1 = field(grid, seed=a.seed, amp=a.amp)
+                rec = dict(tag=a.tag, what="micro_nl", n=n, solver=solver, points=pts, amp=a.amp, seed=a.seed, ka=a.ka,
+                           stages=a.stages, equal=a.equal, start=start, ls=ls)
+                with M.Macroc(argv_of(n, grid, a.ka, a.equal)) as m:
                     m.set_option("micro_mem", 1)
                     m.set_option("micro_nl_solver", solver)
                     if a.poll:
                         m.set_option("micro_grid_poll", a.poll)
+                    if start:  # (left alone at 0, so that the tool also runs against a tree without the options)
+                        m.set_option("micro_nl_start", start)
+                    if ls:
+                        m.set_option("micro_nl_ls", ls)
                     m.set_option("micro_nl_slots", pts)
-                    m.set_u(field(grid, amp=a.amp))
-                    m.set_strains()
-                    first = timed(m, m.homogenize)
-                    dt = timed(m, m.homogenize)
+                    try:
+                        for fac in a.stages[:-1]:
+                            m.set_u(fac * u1)
+                            m.set_strains()
+                            m.homogenize()
+                            m.update_vars()
+                        m.set_u(a.stages[-1] * u1)
+                        m.set_strains()
+                        first = timed(m, m.homogenize)
+                        dt = timed(m, m.homogenize)
+                    except M.MacrocError as e:
+                        print(json.dumps(dict(rec, converged=False, message=str(e))), flush=True)
+                        continue
                     info = m.micro_nl_info()
+                    steps = m.micro_nl_steps() if hasattr(m, "micro_nl_steps") else None
                     dev = m.get_info()["device_bytes"]
                 solved = int(info["path"].sum())
                 cg = info["cg_its"][info["path"] > 0]
-                print(json.dumps(dict(tag=a.tag, what="micro_nl", n=n, solver=solver, points=pts, solved=solved, amp=a.amp, ka=a.ka,
+                print(json.dumps(dict(rec, converged=True, solved=solved,
                                       first_ms=first * 1e3, ms=dt * 1e3, us_per_point=dt * 1e6 / max(solved, 1),
-                                      newton_max=int(info["newton_its"].max()), cg_mean=float(cg.mean()) if solved else 0.0,
+                                      newton_max=int(info["newton_its"].max()), newton=info["newton_its"].tolist()[:8],
+                                      cg_mean=float(cg.mean()) if solved else 0.0,
                                       cg_max=int(info["cg_its"].max()),
                                       us_per_cg_it=dt * 1e6 / max(int(info["cg_its"].max()), 1),
+                                      rejects=int(steps["ls_rejects"].sum()) if steps else 0,
+                                      min_step=float(steps["min_step"][info["path"] > 0].min()) if steps and solved else 1.0,
                                       device_gb=dev / 1e9)), flush=True)
             if a.linear:
                 grid = (a.linear,) * 3
-                with M.Macroc(argv_of(n, grid, a.ka)) as m:
+                with M.Macroc(argv_of(n, grid, a.ka, a.equal)) as m:
                     m.set_option("micro_mem", 1)
                     m.set_option("micro_nl_solver", solver)
                     m.set_u(field(grid, amp=1e-6))
