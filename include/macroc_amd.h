@@ -362,7 +362,18 @@ int mcx_micro_get_phase(void* ctx, unsigned char* phase, int64_t* n);
  * after a step's CG the lengths 2^-j, j = 0 .. K, are tried in turn; trial j is accepted when
  * |D^-1 R_i| at u + 2^-j dx is smaller than at the last accepted iterate, trial K regardless.
  * Both may change at any time, leave micro_n = 2 as it is and are accepted without effect by other
- * laws; the defaults keep every bit. */
+ * laws; the defaults keep every bit.
+ * "micro_nl_tangent" (-micro_nl_tangent seq|block, 0 | 1; default 0; another number fails with code 1,
+ * another word with code 2): how solver 1 runs the six frozen-K_T solves of a solved point's tangent.
+ * 0 runs them one after the other; 1 advances the six columns together, each a CG of its own (its own
+ * vectors, sums, alpha / beta and stop) inside the launches of one CG iteration, which read a micro
+ * Gauss point's tangent data once for all columns.  Every column keeps the sequential solve's
+ * arithmetic and summation order, so sigma, the tangent, f_trial, the histories and the counts of
+ * mcx_micro_nl_get_info are the same bits under both values.  A solve in flight then has 26 vectors
+ * of 3 micro_n^3 doubles instead of 6 and five more sets of work stresses (5 x 6 x 8 (micro_n - 1)^3
+ * doubles), which shrinks the batch of solves that share a launch above micro_n = 20; device_bytes
+ * counts the workspace.  Solver 0 accepts the option without effect and keeps its sequential columns
+ * (its LDS is full), as do other laws.  The value changes only while no history slot is in use. */
 /* per Gauss point (mcx_get_gp_strain's order): path 0 = linear shortcut, 1 = solved; Newton
    iterations, CG iterations (Newton steps and tangent solves together) and the final relative
    Newton residual of the last mcx_homogenize.  Any pointer may be NULL. */
@@ -373,6 +384,10 @@ int mcx_micro_nl_get_pool(void* ctx, int64_t* slots_used, int64_t* slots_allocat
    ("micro_nl_ls") and the smallest accepted length.  A solved point that never backtracked: 0 and
    1.0; a point on the linear shortcut: 0 and 0.0.  Either pointer may be NULL. */
 int mcx_micro_nl_get_steps(void* ctx, int* ls_rejects, double* min_step);
+/* the option "micro_nl_tangent" and, per Gauss point (the same order; col_its[8 nelem][6]), the CG
+   iterations of each of the six tangent columns of the last mcx_homogenize where solver 1 ran them
+   as a block; 0 for every other point.  Either pointer may be NULL. */
+int mcx_micro_nl_get_tangent(void* ctx, int* block, int* col_its);
 
 double mcx_get_displacement(void* ctx, int time_s);
 int mcx_zero_u(void* ctx);                 /* VecZeroEntries(u)  src/init.c:103 */
@@ -439,17 +454,18 @@ int mcx_set_timing(void* ctx, int on);
 int mcx_get_timing(void* ctx, mcx_timing* t);
 int mcx_synchronize(void* ctx);
 /* tuning knobs ("spmv_subl": lines per sub-slab of the SpMV sweep, 0 = whole XCD slab; "micro_rtol",
-   "micro_max_it", "micro_mem", "micro_solver", "micro_grid_poll": the micro cell's CG, -mat_law micro; "micro_nl_rtol", "micro_nl_max_it", "micro_nl_slots", "micro_nl_solver", "micro_nl_start", "micro_nl_ls":
+   "micro_max_it", "micro_mem", "micro_solver", "micro_grid_poll": the micro cell's CG, -mat_law micro; "micro_nl_rtol", "micro_nl_max_it", "micro_nl_slots", "micro_nl_solver", "micro_nl_start", "micro_nl_ls", "micro_nl_tangent":
    -mat_law micro_nl) and a
    device-only SpMV timer (iters launches on the current search direction, HIP events) */
 int mcx_set_option(void* ctx, const char* name, double value);
 /* the command-line flags that have no mcx_opts field, applied to a context through mcx_set_option:
    -micro_mem lds|device ("micro_mem" 0 | 1), -micro_solver cell|grid ("micro_solver" 0 | 1), -micro_nl_solver cell|grid ("micro_nl_solver" 0 | 1),
    -micro_nl_start zero|elastic ("micro_nl_start" 0 | 1), -micro_nl_ls K ("micro_nl_ls", an integer 0 .. 16),
+   -micro_nl_tangent seq|block ("micro_nl_tangent" 0 | 1),
    -micro_rtol, -micro_max_it, -micro_nl_rtol, -micro_nl_max_it, -micro_nl_slots (each with a
    number), -pc_type jacobi|mg ("pc_type" 0 | 1), -pc_mg_levels N, -mg_levels_ksp_max_it k
    ("pc_mg_smooth"), -pc_mg_dist 0|1 ("pc_mg_dist"; give it before -pc_type), -pc_mg_precision
-   double|single ("pc_mg_precision" 0 | 1).  mcx_parse_args accepts these flags and checks -micro_mem's, -micro_solver's, -micro_nl_solver's, -micro_nl_start's, -micro_nl_ls's and -pc_mg_precision's word; call this after mcx_init with the same argv.  Other flags are skipped. */
+   double|single ("pc_mg_precision" 0 | 1).  mcx_parse_args accepts these flags and checks -micro_mem's, -micro_solver's, -micro_nl_solver's, -micro_nl_start's, -micro_nl_ls's, -micro_nl_tangent's and -pc_mg_precision's word; call this after mcx_init with the same argv.  Other flags are skipped. */
 int mcx_apply_args(void* ctx, int argc, const char* const* argv);
 int mcx_time_spmv(void* ctx, int iters, double* avg_ms);
 

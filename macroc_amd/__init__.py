@@ -43,7 +43,7 @@ EXPORTS = [
     "mcx_micro_get_ctan", "mcx_micro_get_phase",
     "mcx_get_gp_ctan", "mcx_micro_nl_get_info", "mcx_micro_nl_get_pool", "mcx_micro_nl_get_steps", "mcx_apply_args",
     "mcx_pc_apply", "mcx_pc_mg_info", "mcx_pc_mg_dump_csr", "mcx_get_st_dma", "mcx_pc_mg_plan", "mcx_pc_mg_box",
-    "mcx_pc_mg_get_precision",
+    "mcx_pc_mg_get_precision", "mcx_micro_nl_get_tangent",
 ]
 
 LAWS = {"elastic": 0, "plastic": 1, "external": 2, "micro": 3, "micro_nl": 4}
@@ -192,6 +192,7 @@ def lib():
     L.mcx_micro_nl_get_info.argtypes = [vp, ip, ip, ip, d]
     L.mcx_micro_nl_get_pool.argtypes = [vp, i64, i64, i64]
     L.mcx_micro_nl_get_steps.argtypes = [vp, ip, d]
+    L.mcx_micro_nl_get_tangent.argtypes = [vp, ip, ip]
     for fn in ("mcx_set_gp_stress", "mcx_set_gp_ctan", "mcx_get_gp_strain", "mcx_get_gp_ctan"):
         getattr(L, fn).argtypes = [vp, d]
     L.mcx_micro_get_ctan.argtypes = [vp, d, C.POINTER(C.c_int), d]
@@ -497,6 +498,21 @@ class Macroc:
         _check(lib().mcx_micro_nl_get_steps(self._ctx, rej.ctypes.data_as(C.POINTER(C.c_int)), _dp(ms)),
                "mcx_micro_nl_get_steps")
         return {"ls_rejects": rej, "min_step": ms}
+
+    def micro_nl_tangent(self):
+        """the option micro_nl_tangent: 0 (seq) the six tangent columns of a solved point one after the
+        other, 1 (block) micro_nl_solver 1 advances them together."""
+        block = C.c_int(0)
+        _check(lib().mcx_micro_nl_get_tangent(self._ctx, C.byref(block), None), "mcx_micro_nl_get_tangent")
+        return block.value
+
+    def micro_nl_tangent_its(self):
+        """[ngp][6] (gpi order): the CG iterations of each tangent column of the last homogenize where
+        micro_nl_solver 1 ran the columns as a block (micro_nl_tangent 1); 0 for every other point."""
+        its = np.zeros((self.ngp, 6), np.int32)
+        _check(lib().mcx_micro_nl_get_tangent(self._ctx, None, its.ctypes.data_as(C.POINTER(C.c_int))),
+               "mcx_micro_nl_get_tangent")
+        return its
 
     # ---- the micro-scale cell (-mat_law micro)
     def micro_ctan(self):

@@ -260,6 +260,7 @@ static int init_ctx(Ctx& c, const mcx_opts* o, int rank, int nranks, const void*
         (rc = dalloc(c, &c.mnl_list, ngp)) || (rc = dalloc(c, &c.mnl_cnt, 4)) ||
         (rc = dalloc(c, &c.mnl_its, 4 * ngp)) || (rc = dalloc(c, &c.mnl_rn, 2 * ngp)))
       return rc;
+    c.mnl_col_its.assign((size_t)(6 * ngp), 0);
     MCX_HIP(hipMemsetAsync(c.mnl_slot, 0xff, sizeof(int) * (ngp > 0 ? ngp : 1), c.stream));  // -1: no slot
     c.mnl_Sy[0] = o->micro_mat_1[2];
     c.mnl_Ka[0] = o->micro_mat_1[3];
@@ -400,6 +401,7 @@ using namespace mcx;
 static const char* const kApplyFlags[] = {"-micro_mem",     "-micro_rtol",      "-micro_max_it",  "-micro_nl_rtol",
                                           "-micro_nl_max_it", "-micro_nl_slots", "-micro_solver",
                                           "-micro_nl_solver", "-micro_nl_start",  "-micro_nl_ls",
+                                          "-micro_nl_tangent",
                                           "-pc_type",       "-pc_mg_levels",    "-mg_levels_ksp_max_it",
                                           "-pc_mg_dist",    "-pc_mg_precision"};
 static bool apply_flag(const char* k) {
@@ -553,6 +555,10 @@ int mcx_parse_args(mcx_opts* o, int argc, const char* const* argv) try {
       }
       if (!std::strcmp(k, "-micro_nl_ls") && !micro_nl_ls_word(v)) {
         set_error(std::string("-micro_nl_ls: an integer 0 .. 16, got ") + (v ? v : "(none)"));
+        return 2;
+      }
+      if (!std::strcmp(k, "-micro_nl_tangent") && (!v || (std::strcmp(v, "seq") && std::strcmp(v, "block")))) {
+        set_error(std::string("-micro_nl_tangent: seq or block, got ") + (v ? v : "(none)"));
         return 2;
       }
       if (!std::strcmp(k, "-pc_mg_precision") && (!v || (std::strcmp(v, "double") && std::strcmp(v, "single")))) {
@@ -723,6 +729,21 @@ int mcx_pc_mg_get_precision(void* ctx, int* single) try {
   GUARD(ctx);
   CTX(ctx);
   if (single) *single = c.pc_mg_precision;
+  return 0;
+} MCX_CATCH
+
+int mcx_micro_nl_get_tangent(void* ctx, int* block, int* col_its) try {
+  MCX_ENTRY();
+  GUARD(ctx);
+  CTX(ctx);
+  if (block) *block = c.mnl_tangent;
+  if (col_its) {  // [8 nelem][6], Gauss points in the order of mcx_micro_nl_get_info
+    const int64_t E = c.g.nelem, ngp = 8 * E;
+    for (int64_t e = 0; e < E; e++)
+      for (int gp = 0; gp < 8; gp++)
+        for (int l = 0; l < 6; l++)
+          col_its[(e * 8 + gp) * 6 + l] = c.mnl_col_its.empty() ? 0 : c.mnl_col_its[(size_t)(l * ngp + gp * E + e)];
+  }
   return 0;
 } MCX_CATCH
 
@@ -938,9 +959,15 @@ static int micro_resize(Ctx& c, double** p, int64_t* bytes, int64_t want) {
 // that changes nothing and the results do not depend on micro_grid_poll.
 // solves of micro_nl_solver 1 that share a launch: what keeps the vectors within 512 MiB, at most 64 and
 // at most the local Gauss points (64 from n = 2 to 33, 13 at n = 64); micro_mem_blocks > 0 replaces it
+// Under micro_nl_tangent 1 a solve has 26 vectors, not 6, within the same 512 MiB, and the
+// five more sets of work stresses have a budget of their own, 1536 MiB (64 / 64 / 23 / 3 solves at
+// n = 10 / 20 / 33 / 64)
+static bool mnl_block(const Ctx& c) { return c.mnl_tangent == 1 && c.mnl_solver == 1 && c.mat.law == MCX_LAW_MICRO_NL; }
 static int64_t mnl_grid_batch(const Ctx& c) {
-  const int64_t n = c.micro.n, per = (int64_t)sizeof(double) * MNLG_NVEC * 3 * n * n * n;
-  const int64_t b = c.mnl_ws_blocks_opt > 0 ? c.mnl_ws_blocks_opt : std::min<int64_t>(64, ((int64_t)512 << 20) / per);
+  const int64_t n = c.micro.n, per = (int64_t)sizeof(double) * MNLG_NVEC * 3 * n * n * n + (mnl_block(c) ? mnlb_vec_bytes((int)n) : 0);
+  int64_t b = std::min<int64_t>(64, ((int64_t)512 << 20) / per);
+  if (mnl_block(c) && n > 1) b = std::min<int64_t>(b, ((int64_t)1536 << 20) / mnlb_sig_bytes((int)n));
+  if (c.mnl_ws_blocks_opt > 0) b = c.mnl_ws_blocks_opt;
   return std::max<int64_t>(1, std::min<int64_t>(b, std::max<int64_t>(1, 8 * c.g.nelem)));
 }
 
@@ -948,7 +975,9 @@ static int64_t mnl_grid_batch(const Ctx& c) {
 // micro_nl_solver 1 the listed points' (mnlg_layout) in the same memory at another time
 static int64_t grid_ws_bytes(const Ctx& c) {
   const int64_t lin = mg_ws_bytes(c.micro.n);
-  return micro_nl_grid(c) ? std::max(lin, mnlg_ws_bytes(c.micro.n, mnl_grid_batch(c))) : lin;
+  if (!micro_nl_grid(c)) return lin;
+  const int64_t batch = mnl_grid_batch(c);
+  return std::max(lin, mnlg_ws_bytes(c.micro.n, batch) + (mnl_block(c) ? mnlb_ws_bytes(c.micro.n, batch) : 0));
 }
 
 static int solve_micro_grid(Ctx& c, const MicroArgs& m) {
@@ -1053,6 +1082,9 @@ static int solve_mnl_grid(Ctx& c, const MicroNlArgs& a, int nsolve) {
   const int64_t batch = mnl_grid_batch(c);
   if (int rc = micro_resize(c, &c.micro_grid_ws, &c.micro_grid_bytes, grid_ws_bytes(c))) return rc;
   const MnlGridWs w = mnlg_layout(c.micro_grid_ws, a.m.n, batch);
+  const bool block = mnl_block(c);  // option micro_nl_tangent 1: the six columns of a solve as one block
+  const MnlBlockWs bw = block ? mnlb_layout(c.micro_grid_ws, a.m.n, batch) : MnlBlockWs{};
+  std::vector<MnlBlockCol> hc(block ? (size_t)batch * 6 : 0);
   const int per = std::max(1, std::min(c.micro_grid_poll, a.m.max_it));
   // a solve has at most nl_max_it + 1 state passes and six columns, each CG at most max_it iterations
   // (and, globalised, one more pass for the predictor and up to nl_ls more per step)
@@ -1064,9 +1096,15 @@ static int solve_mnl_grid(Ctx& c, const MicroNlArgs& a, int nsolve) {
     launch_mnlg_start(c, w, base, cnt);
     bool newton_pass = true;  // a solve of the batch is at a Newton state pass (all are, at the start)
     for (int64_t round = 0;; round++) {
-      launch_mnlg_transition(c, a, w, cnt);
-      if (globalised && newton_pass) launch_mnlg_transition(c, a, w, cnt);
-      for (int q = 0; q < per; q++) launch_mnlg_iterate(c, a, w, cnt);
+      if (block) {
+        launch_mnlb_transition(c, a, w, bw, cnt);
+        if (globalised && newton_pass) launch_mnlb_transition(c, a, w, bw, cnt);
+        for (int q = 0; q < per; q++) launch_mnlb_iterate(c, a, w, bw, cnt);
+      } else {
+        launch_mnlg_transition(c, a, w, cnt);
+        if (globalised && newton_pass) launch_mnlg_transition(c, a, w, cnt);
+        for (int q = 0; q < per; q++) launch_mnlg_iterate(c, a, w, cnt);
+      }
       MCX_HIP(hipGetLastError());
       MCX_HIP(hipMemcpyAsync(h.data(), w.st, sizeof(MnlGridState) * cnt, hipMemcpyDeviceToHost, c.stream));
       MCX_HIP(hipStreamSynchronize(c.stream));
@@ -1081,6 +1119,13 @@ static int solve_mnl_grid(Ctx& c, const MicroNlArgs& a, int nsolve) {
         set_error("-mat_law micro_nl: micro_nl_solver 1 did not end within its iteration limits (internal error)");
         return 35;
       }
+    }
+    if (block) {  // the columns' own counts, for mcx_micro_nl_get_tangent (a solve that Newton failed never started them)
+      const int64_t ngp = 8 * c.g.nelem;
+      MCX_HIP(hipMemcpyAsync(hc.data(), bw.col, sizeof(MnlBlockCol) * 6 * cnt, hipMemcpyDeviceToHost, c.stream));
+      MCX_HIP(hipStreamSynchronize(c.stream));
+      for (int s = 0; s < cnt; s++)
+        for (int l = 0; l < 6 && h[s].lc == 6; l++) c.mnl_col_its[(size_t)(l * ngp + h[s].q)] = hc[(size_t)s * 6 + l].its;
     }
   }
   return 0;
@@ -1122,6 +1167,7 @@ static int micro_nl_homogenize(Ctx& c) {
     set_error(buf);
     return 34;
   }
+  c.mnl_col_its.assign(c.mnl_col_its.size(), 0);
   if (h[1] == 0) return 0;
   if (!c.mnl_pool) {
     MCX_HIP(hipMalloc((void**)&c.mnl_pool, (size_t)(c.mnl_cap * bytes)));
@@ -2356,6 +2402,23 @@ int mcx_set_option(void* ctx, const char* name, double value) try {
     if (!c.mnl_solver) return micro_resize(c, &c.micro_grid_ws, &c.micro_grid_bytes, 0);
     return 0;
   }
+  if (!std::strcmp(name, "micro_nl_tangent")) {  // how solver 1 runs a point's six tangent columns
+    if (value != 0. && value != 1.) {
+      set_error("micro_nl_tangent: 0 (seq: the six tangent columns one after the other) or 1 (block: micro_nl_solver 1 "
+                "advances them together, 26 vectors of 3 micro_n^3 per solve in flight)");
+      return 1;
+    }
+    if ((int)value == c.mnl_tangent) return 0;
+    if (c.mnl_used > 0) {  // the workspace's layout follows the option: micro_nl_solver's rule
+      set_error("micro_nl_tangent: " + std::to_string(c.mnl_used) +
+                " history slots are in use; the tangent solves are chosen before the first non-linear point");
+      return 2;
+    }
+    c.mnl_tangent = (int)value;  // solver 0 and the other laws: accepted, no effect
+    // solver 1: the workspace follows the option (grid_ws_bytes), now if there is one, else at the next solve
+    if (micro_nl_grid(c) && c.micro_grid_ws) return micro_resize(c, &c.micro_grid_ws, &c.micro_grid_bytes, grid_ws_bytes(c));
+    return 0;
+  }
   if (!std::strcmp(name, "pc_mg_dist")) {  // 1: pc_type 1 on a context with a communicator (the distributed hierarchy)
     if (value != 0. && value != 1.) {
       set_error("pc_mg_dist: 0 (pc_type mg on one rank only) or 1 (the hierarchy distributed over the ranks)");
@@ -2847,6 +2910,12 @@ int mcx_apply_args(void* ctx, int argc, const char* const* argv) try {
         return 2;
       }
       value = std::atof(v);
+    } else if (!std::strcmp(k, "-micro_nl_tangent")) {
+      if (std::strcmp(v, "seq") && std::strcmp(v, "block")) {
+        set_error(std::string("-micro_nl_tangent: seq or block, got ") + v);
+        return 2;
+      }
+      value = std::strcmp(v, "block") ? 0. : 1.;
     } else if (!std::strcmp(k, "-pc_mg_precision")) {
       if (std::strcmp(v, "double") && std::strcmp(v, "single")) {
         set_error(std::string("-pc_mg_precision: double or single, got ") + v);

@@ -1155,11 +1155,10 @@ __device__ __forceinline__ void mnl_apply_tangent(double* __restrict__ ws, const
 }
 
 // y = sum over the node's elements (ascending) and their Gauss points of B_a^T sigma detJ, from
-// the slot's work stresses
-__device__ __forceinline__ void mnl_gather(const double* __restrict__ ws, const double* __restrict__ sdn, int n, int i,
-                                           int j, int k, double detJ, double (&y)[3]) {
+// a set of six work stresses sg ([6][8 (n-1)^3])
+__device__ __forceinline__ void mnl_gather_sig(const double* __restrict__ sg, const double* __restrict__ sdn, int n, int i,
+                                               int j, int k, double detJ, double (&y)[3]) {
   const int ne = n - 1, nmgp = 8 * ne * ne * ne;
-  const double* sg = ws + (size_t)MNL_SIG * nmgp;
   y[0] = y[1] = y[2] = 0.;
 #pragma unroll 1
   for (int oz = 1; oz >= 0; oz--) {
@@ -1187,6 +1186,13 @@ __device__ __forceinline__ void mnl_gather(const double* __restrict__ ws, const 
       }
     }
   }
+}
+
+// ... from the slot's work stresses
+__device__ __forceinline__ void mnl_gather(const double* __restrict__ ws, const double* __restrict__ sdn, int n, int i,
+                                           int j, int k, double detJ, double (&y)[3]) {
+  const int ne = n - 1, nmgp = 8 * ne * ne * ne;
+  mnl_gather_sig(ws + (size_t)MNL_SIG * nmgp, sdn, n, i, j, k, detJ, y);
 }
 
 // the diagonal of K_T at node (i, j, k) from the slot's tangent data
@@ -2212,11 +2218,15 @@ __device__ __forceinline__ void mnlg_end(MnlGridState& st, int64_t ngp, int* __r
 //   PHASE 1  after q = K_T p: pq, alpha; !(pq > 0) ends the solve unconverged
 //   PHASE 2  after the x / r update: the iteration count; converged -> the next transition; else beta
 //   PHASE 3  a tangent solve starts: norm0, rz; converged at once when the norm is 0
-template <int PHASE>
+//   PHASE 4  PHASE 0 under option micro_nl_tangent 1: a converged Newton loop hands the solve to the
+//            block of six columns (stage MNLG_BSTART, the k_mnlb_* kernels below) instead of to column 0
+template <int PHASE_>
 __global__ __launch_bounds__(MICRO_TPB) void k_mnlg_scalar(MicroNlArgs a, MnlGridWs w, int cnt, int64_t ngp,
                                                            double* __restrict__ sig, double* __restrict__ ctan,
                                                            double* __restrict__ ftrial, int* __restrict__ its_out,
                                                            double* __restrict__ rn_out, int* __restrict__ fail) {
+  constexpr int PHASE = PHASE_ == 4 ? 0 : PHASE_;
+  constexpr bool BLOCK = PHASE_ == 4;
   __shared__ double sred[2 * (MICRO_TPB / 64)];
   const int tid = threadIdx.x, s = blockIdx.x;
   MnlGridState& st = w.st[s];
@@ -2275,7 +2285,7 @@ __global__ __launch_bounds__(MICRO_TPB) void k_mnlg_scalar(MicroNlArgs a, MnlGri
         for (int k = 0; k < 6; k++) sig[k * ngp + st.q] = sg[k];
         ftrial[st.q] = fmax;
         st.lc = 0;
-        st.stage = MNLG_TSTART;
+        st.stage = BLOCK ? MNLG_BSTART : MNLG_TSTART;
       } else if (st.nits >= a.nl_max_it) {
         st.status = 1;
         mnlg_end(st, ngp, its_out, rn_out, fail);
@@ -2375,6 +2385,436 @@ __global__ __launch_bounds__(MICRO_TPB) void k_mnlg_pupdate(MicroNlArgs a, MnlGr
   if (d >= ndof) return;
   double* const sp = mnlg_vec(w, s, 3, ndof);
   sp[d] = mnlg_vec(w, s, 5, ndof)[d] * mnlg_vec(w, s, 2, ndof)[d] + w.st[s].beta * sp[d];
+}
+
+// ---------------------------------------------------------------------------- the six tangent columns as one block
+// option micro_nl_tangent 1.  The six frozen-K_T solves of a point are independent CGs on
+// one operator; here they advance together, column l with its own vectors, work stresses, partial
+// sums and record (MnlBlockCol), so every column runs the statements of the sequential kernels above
+// in their order and gives their bits.  Nothing is summed across columns.  A solve's stages are
+// MNLG_BSTART (Newton has converged: the six columns start), MNLG_BCG (they iterate; a column that
+// has ended is gated out by its done flag) and MNLG_BTRANS (all have ended: the tangent is formed).
+// The iteration's kernels also serve a Newton CG (stage MNLG_CG) as a block of column 0 alone with
+// the solve's own scalars, so that an iteration stays six launches whatever the solves are doing.
+__device__ __forceinline__ double* mnlb_vec(const MnlGridWs& w, const MnlBlockWs& bw, int s, int l, int v, int64_t ndof) {
+  return l == 0 ? mnlg_vec(w, s, v, ndof)  // v: 1 x, 2 r, 3 p, 4 q
+                : bw.vec + (((size_t)s * 5 + (l - 1)) * 4 + (v - 1)) * (size_t)ndof;
+}
+__device__ __forceinline__ double* mnlb_sig(double* slot_ws, const MnlBlockWs& bw, int s, int l, size_t nmgp) {
+  return l == 0 ? slot_ws + (size_t)MNL_SIG * nmgp : bw.sig + ((size_t)s * 5 + (l - 1)) * 6 * nmgp;
+}
+__device__ __forceinline__ double* mnlb_part(const MnlGridWs& w, const MnlBlockWs& bw, int s, int l, int q) {
+  return bw.part + (((size_t)s * 6 + l) * MNLB_NPART + q) * (size_t)w.npart;
+}
+
+// one thread per node: x_l = E_l x on the boundary, 0 inside, for the six columns (k_mnlg_prep<true>'s statement)
+__global__ __launch_bounds__(MICRO_TPB) void k_mnlb_prep(MicroNlArgs a, MnlGridWs w, MnlBlockWs bw) {
+  const int s = blockIdx.y;
+  if (w.st[s].stage != MNLG_BSTART) return;
+  const int n = a.m.n, ne = n - 1, nn = n * n * n;
+  const int nd = blockIdx.x * MICRO_TPB + threadIdx.x;
+  if (nd >= nn) return;
+  const int64_t ndof = 3 * (int64_t)nn;
+  const int i = nd % n, j = (nd / n) % n, k = nd / (n * n);
+  const bool bnd = i == 0 || j == 0 || k == 0 || i == ne || j == ne || k == ne;
+  const double X[3] = {(double)i / (double)ne, (double)j / (double)ne, (double)k / (double)ne};
+#pragma unroll 1
+  for (int lc = 0; lc < 6; lc++) {
+    double* const sx = mnlb_vec(w, bw, s, lc, 1, ndof);
+    const int p = lc == 5 ? 1 : 0, p2 = lc == 3 ? 1 : 2;  // xy: (0, 1), xz: (0, 2), yz: (1, 2)
+#pragma unroll
+    for (int r = 0; r < 3; r++) {
+      double Eb[3];
+#pragma unroll
+      for (int d = 0; d < 3; d++)
+        Eb[d] = lc < 3 ? ((r == lc && d == lc) ? 1. : 0.) : (((r == p && d == p2) || (r == p2 && d == p)) ? 0.5 : 0.);
+      sx[3 * (size_t)nd + r] = bnd ? Eb[0] * X[0] + Eb[1] * X[1] + Eb[2] * X[2] : 0.;
+    }
+  }
+}
+
+// The Gauss-point pass of the block over a tile of MG_T^3 elements: k_mnlg_gp's thread layout and
+// products.  The tile's layers go in passes of MNLB_LZ; a thread loads the tangent data (theta,
+// theta-bar, n) of its MNLB_LZ micro Gauss points of the pass from the slot once, into registers,
+// and then walks the active columns: the workgroup restages the column's (MG_T + 1)^3 source nodes
+// in LDS (component-major, as there) and every thread leaves the column's six stresses in the
+// column's work set, the micro Gauss point index fastest.
+//   WHICH 0  a CG iteration: sigma_l = C_gp B p_l for the columns not done (a Newton CG: column 0)
+//   WHICH 1  the block has ended: sigma_l = C_gp B x_l and the tile's six stress sums per column
+//            (one pass of MG_T layers, the tangent data read per column: a thread's sum runs over
+//            the layers in k_mnlg_gp<1>'s order)
+//   WHICH 2  the block starts: sigma_l = C_gp B x_l of the boundary values
+constexpr int MNLB_LZ = 2;
+template <int WHICH>
+__global__ __launch_bounds__(MICRO_TPB, 4) void k_mnlb_gp(MicroNlArgs a, MnlGridWs w, MnlBlockWs bw, double* __restrict__ pool) {
+  constexpr int P = MG_T + 1, P3 = P * P * P;
+  constexpr int LZ = WHICH == 1 ? MG_T : MNLB_LZ;
+  __shared__ double sv[3 * P3];
+  __shared__ double sdn[8 * 24];
+  __shared__ double sred[2 * (MICRO_TPB / 64)];
+  const int tid = threadIdx.x, s = blockIdx.y;
+  const MnlGridState& st = w.st[s];
+  const bool newton = WHICH == 0 && st.stage == MNLG_CG;
+  if (!newton && st.stage != (WHICH == 0 ? MNLG_BCG : WHICH == 1 ? MNLG_BTRANS : MNLG_BSTART)) return;  // the whole workgroup
+  const MnlBlockCol* const col = bw.col + 6 * (size_t)s;
+  const int ncol = newton ? 1 : 6, cpw = 6 / (int)gridDim.z, l0 = (int)blockIdx.z * cpw, l1 = min(l0 + cpw, ncol);
+  if (l0 >= l1) return;  // the whole workgroup: grid z splits the six columns, a Newton CG has one
+  const int n = a.m.n, ne = n - 1, nel = ne * ne * ne, nt = w.ntile, tile = blockIdx.x;
+  const size_t nmgp = 8 * (size_t)nel;
+  const int64_t ndof = 3 * (int64_t)n * n * n;
+  const int ox = MG_T * (tile % nt), oy = MG_T * ((tile / nt) % nt), oz = MG_T * (tile / (nt * nt));
+  double* const ws = pool + (size_t)st.slot * MNL_WS * nmgp;
+  const double detJ = 1. / (8. * (double)nel);
+  const double Gp[2] = {a.m.E[0] / (2. * (1. + a.m.nu[0])), a.m.E[1] / (2. * (1. + a.m.nu[1]))};
+  const double Kp[2] = {a.m.E[0] / (3. * (1. - 2. * a.m.nu[0])), a.m.E[1] / (3. * (1. - 2. * a.m.nu[1]))};
+  for (int t = tid; t < 8 * 24; t += MICRO_TPB) sdn[t] = mnl_dn(t, ne);
+  const int gp = tid & 7, lx = (tid >> 3) & 7, ly = tid >> 6, ei = ox + lx, ej = oy + ly;
+  const bool mine = ei < ne && ej < ne;
+#pragma unroll 1
+  for (int lz0 = 0; lz0 < MG_T; lz0 += LZ) {
+    if (oz + lz0 >= ne) break;  // the whole workgroup
+    double th[LZ], thb[LZ], nv[LZ][6];
+    if (WHICH != 1 && mine) {
+#pragma unroll
+      for (int q = 0; q < LZ; q++) {
+        const int ek = oz + lz0 + q;
+        if (ek < ne) {
+          const size_t mg = 8 * ((size_t)ei + (size_t)ne * ((size_t)ej + (size_t)ne * (size_t)ek)) + gp;
+          th[q] = ws[(size_t)MNL_TAN * nmgp + mg];
+          thb[q] = ws[(size_t)(MNL_TAN + 1) * nmgp + mg];
+#pragma unroll
+          for (int b = 0; b < 6; b++) nv[q][b] = ws[(size_t)(MNL_TAN + 2 + b) * nmgp + mg];
+        }
+      }
+    }
+#pragma unroll 1
+    for (int l = l0; l < l1; l++) {
+      if (WHICH == 0 && !newton && col[l].done) continue;  // the whole workgroup
+      const double* const src = mnlb_vec(w, bw, s, l, WHICH == 0 ? 3 : 1, ndof);
+      double* const sgl = mnlb_sig(ws, bw, s, l, nmgp);
+      __syncthreads();  // sdn is written; the column before has been read
+      for (int h = lz0 * P * P + tid; h < (lz0 + LZ + 1) * P * P; h += MICRO_TPB) {  // the pass' LZ + 1 layers of nodes
+        const int gi = ox + h % P, gj = oy + (h / P) % P, gk = oz + h / (P * P);
+        const bool in = gi < n && gj < n && gk < n;
+        const size_t nd = in ? (size_t)gi + (size_t)n * ((size_t)gj + (size_t)n * (size_t)gk) : 0;
+#pragma unroll
+        for (int r = 0; r < 3; r++) sv[r * P3 + h] = in ? src[3 * nd + r] : 0.;
+      }
+      __syncthreads();
+      double sg[6] = {0., 0., 0., 0., 0., 0.};
+      if (mine) {
+        if (WHICH == 1) {
+#pragma unroll 1
+          for (int lz = 0; lz < MG_T; lz++) {
+            const int ek = oz + lz;
+            if (ek >= ne) break;
+            const int ph = micro_phase(a.m.type, ne, ei, ej, ek);
+            const size_t mg = 8 * ((size_t)ei + (size_t)ne * ((size_t)ej + (size_t)ne * (size_t)ek)) + gp;
+            double ee[6], nvl[6], sgm[6];
+            mnlg_strain(sdn + 24 * gp, sv, lx, ly, lz, ee);
+            const double thl = ws[(size_t)MNL_TAN * nmgp + mg], thbl = ws[(size_t)(MNL_TAN + 1) * nmgp + mg];
+#pragma unroll
+            for (int b = 0; b < 6; b++) nvl[b] = ws[(size_t)(MNL_TAN + 2 + b) * nmgp + mg];
+            mnl_Cmul(ph ? Gp[1] : Gp[0], ph ? Kp[1] : Kp[0], thl, thbl, nvl, ee, sgm);
+#pragma unroll
+            for (int k = 0; k < 6; k++) {
+              sgl[(size_t)k * nmgp + mg] = sgm[k];
+              sg[k] += sgm[k] * detJ;
+            }
+          }
+        } else {
+#pragma unroll
+          for (int q = 0; q < LZ; q++) {
+            const int lz = lz0 + q, ek = oz + lz;
+            if (ek < ne) {
+              const int ph = micro_phase(a.m.type, ne, ei, ej, ek);
+              const size_t mg = 8 * ((size_t)ei + (size_t)ne * ((size_t)ej + (size_t)ne * (size_t)ek)) + gp;
+              double ee[6], sgm[6];
+              mnlg_strain(sdn + 24 * gp, sv, lx, ly, lz, ee);
+              mnl_Cmul(ph ? Gp[1] : Gp[0], ph ? Kp[1] : Kp[0], th[q], thb[q], nv[q], ee, sgm);
+#pragma unroll
+              for (int k = 0; k < 6; k++) sgl[(size_t)k * nmgp + mg] = sgm[k];
+            }
+          }
+        }
+      }
+      if (WHICH == 1) {
+        micro_reduce2(sg[0], sg[1], sred);
+        micro_reduce2(sg[2], sg[3], sred);
+        micro_reduce2(sg[4], sg[5], sred);
+        if (tid == 0) {
+#pragma unroll
+          for (int k = 0; k < 6; k++) mnlb_part(w, bw, s, l, 2 + k)[tile] = sg[k];
+        }
+      }
+    }
+  }
+}
+
+// The node gather of the block over a tile of MG_T^3 nodes, column by column from the column's work
+// stresses: k_mnlg_gather's statements.  INIT (the block starts): r_l, p_l = z_l, q_l = 0, the tile's
+// r.z and z.z; else q_l = K_T p_l on the interior and the tile's p.q, for the columns not done (a
+// Newton CG: column 0).
+template <bool INIT>
+__global__ __launch_bounds__(MICRO_TPB) void k_mnlb_gather(MicroNlArgs a, MnlGridWs w, MnlBlockWs bw, double* __restrict__ pool) {
+  __shared__ double sdn[8 * 24];
+  __shared__ double sred[2 * (MICRO_TPB / 64)];
+  const int tid = threadIdx.x, s = blockIdx.y;
+  const MnlGridState& st = w.st[s];
+  const bool newton = !INIT && st.stage == MNLG_CG;
+  if (!newton && st.stage != (INIT ? MNLG_BSTART : MNLG_BCG)) return;
+  const MnlBlockCol* const col = bw.col + 6 * (size_t)s;
+  const int ncol = newton ? 1 : 6, cpw = 6 / (int)gridDim.z, l0 = (int)blockIdx.z * cpw, l1 = min(l0 + cpw, ncol);
+  if (l0 >= l1) return;  // the whole workgroup: grid z splits the six columns, a Newton CG has one
+  const int n = a.m.n, ne = n - 1, nel = ne * ne * ne, nt = w.ntile, tile = blockIdx.x;
+  const size_t nmgp = 8 * (size_t)nel;
+  const int64_t ndof = 3 * (int64_t)n * n * n;
+  const double detJ = 1. / (8. * (double)nel);
+  double* const ws = pool + (size_t)st.slot * MNL_WS * nmgp;
+  for (int t = tid; t < 8 * 24; t += MICRO_TPB) sdn[t] = mnl_dn(t, ne);
+  __syncthreads();
+  const int i = MG_T * (tile % nt) + tid % MG_T, j = MG_T * ((tile / nt) % nt) + (tid / MG_T) % MG_T,
+            k = MG_T * (tile / (nt * nt)) + tid / (MG_T * MG_T);
+  const bool in = i < n && j < n && k < n;
+  const bool bnd = i == 0 || j == 0 || k == 0 || i == ne || j == ne || k == ne;
+  const size_t nd = in ? (size_t)i + (size_t)n * ((size_t)j + (size_t)n * (size_t)k) : 0;
+  const double* const sd = mnlg_vec(w, s, 5, ndof);
+#pragma unroll 1
+  for (int l = l0; l < l1; l++) {
+    if (!INIT && !newton && col[l].done) continue;  // the whole workgroup
+    double y[3] = {0., 0., 0.};
+    if (in && !bnd) mnl_gather_sig(mnlb_sig(ws, bw, s, l, nmgp), sdn, n, i, j, k, detJ, y);
+    double s0 = 0., s1 = 0.;
+    if (INIT) {
+      if (in) {
+        double* const sr = mnlb_vec(w, bw, s, l, 2, ndof);
+        double* const sp = mnlb_vec(w, bw, s, l, 3, ndof);
+        double* const sq = mnlb_vec(w, bw, s, l, 4, ndof);
+#pragma unroll
+        for (int r = 0; r < 3; r++) {
+          const double rr = bnd ? 0. : -y[r], z = sd[3 * nd + r] * rr;
+          sr[3 * nd + r] = rr;
+          sp[3 * nd + r] = z;
+          sq[3 * nd + r] = 0.;
+          s0 += rr * z;
+          s1 += z * z;
+        }
+      }
+    } else if (in && !bnd) {
+      const double* const sp = mnlb_vec(w, bw, s, l, 3, ndof);
+      double* const sq = mnlb_vec(w, bw, s, l, 4, ndof);
+#pragma unroll
+      for (int r = 0; r < 3; r++) {
+        sq[3 * nd + r] = y[r];
+        s0 += sp[3 * nd + r] * y[r];
+      }
+    }
+    micro_reduce2(s0, s1, sred);
+    if (tid == 0) {
+      mnlb_part(w, bw, s, l, 0)[tile] = s0;
+      if (INIT) mnlb_part(w, bw, s, l, 1)[tile] = s1;
+    }
+  }
+}
+
+// The scalar steps of the block, one workgroup per solve, column after column: each column's partials
+// in ascending order strided over the threads, then micro_reduce2's tree (k_mnlg_scalar's sums),
+// and thread 0 runs the column's own alpha / beta / stop logic on the column's record.
+//   PHASE 0  the block has ended (MNLG_BTRANS): column l of the tangent from column l's stress sums;
+//            the CG count takes the six columns' iterations; a column that ended unconverged fails the
+//            point (status 2), else the symmetrised tangent ends it
+//   PHASE 1  after q = K_T p: pq, alpha per column; !(pq > 0) ends the column unconverged
+//   PHASE 2  after the x / r update: the column's count; converged or out of iterations -> done; else beta
+//   PHASE 3  the block starts (MNLG_BSTART): norm0, rz per column; a column whose norm is 0 is done at once
+// PHASE 1 and 2 carry a Newton CG (MNLG_CG) with k_mnlg_scalar's statements on the solve's record,
+// its partials being column 0's.  When the last column is done the solve goes to MNLG_BTRANS.
+template <int PHASE>
+__global__ __launch_bounds__(MICRO_TPB) void k_mnlb_scalar(MicroNlArgs a, MnlGridWs w, MnlBlockWs bw, int cnt, int64_t ngp,
+                                                           double* __restrict__ ctan, int* __restrict__ its_out,
+                                                           double* __restrict__ rn_out, int* __restrict__ fail) {
+  __shared__ double sred[2 * (MICRO_TPB / 64)];
+  const int tid = threadIdx.x, s = blockIdx.x;
+  MnlGridState& st = w.st[s];
+  const bool newton = (PHASE == 1 || PHASE == 2) && st.stage == MNLG_CG;
+  if (!newton && st.stage != (PHASE == 0 ? MNLG_BTRANS : PHASE == 3 ? MNLG_BSTART : MNLG_BCG)) return;
+  MnlBlockCol* const col = bw.col + 6 * (size_t)s;
+  if (newton) {
+    const double* const p0 = mnlb_part(w, bw, s, 0, 0);
+    const double* const p1 = mnlb_part(w, bw, s, 0, 1);
+    double sa = 0., sb = 0.;
+    for (int q = tid; q < cnt; q += MICRO_TPB) {
+      sa += p0[q];
+      if (PHASE != 1) sb += p1[q];
+    }
+    micro_reduce2(sa, sb, sred);
+    if (tid != 0) return;
+    if (PHASE == 1) {
+      st.pq = sa;
+      if (!(sa > 0.)) {  // no curvature left along p: reported as not converged
+        st.cgits += st.its;
+        st.status = 2;
+        mnlg_end(st, ngp, its_out, rn_out, fail);
+      } else {
+        st.alpha = st.rz / sa;
+      }
+    } else {
+      st.its++;
+      if (sqrt(sb) / st.norm0 <= a.m.rtol) {
+        st.cgits += st.its;
+        st.nits++;
+        if (a.nl_ls > 0) st.trial = 0, st.lam = 1.;
+        st.stage = MNLG_TRANS;
+      } else {
+        st.beta = sa / st.rz;
+        st.rz = sa;
+        if (!(st.its < a.m.max_it)) {
+          st.cgits += st.its;
+          st.status = 2;
+          mnlg_end(st, ngp, its_out, rn_out, fail);
+        }
+      }
+    }
+    return;
+  }
+  bool alldone = true;  // thread 0's
+#pragma unroll 1
+  for (int l = 0; l < 6; l++) {
+    MnlBlockCol& c = col[l];
+    if ((PHASE == 1 || PHASE == 2) && c.done) continue;  // the whole workgroup: c is written after the sums below
+    if (PHASE == 0) {
+      double sg[6] = {0., 0., 0., 0., 0., 0.};
+#pragma unroll
+      for (int k = 0; k < 6; k++) {
+        const double* const p = mnlb_part(w, bw, s, l, 2 + k);
+        for (int q = tid; q < cnt; q += MICRO_TPB) sg[k] += p[q];
+      }
+      micro_reduce2(sg[0], sg[1], sred);
+      micro_reduce2(sg[2], sg[3], sred);
+      micro_reduce2(sg[4], sg[5], sred);
+      if (tid == 0) {
+        // column l of the tangent: the volume average of C_gp B w
+#pragma unroll
+        for (int k = 0; k < 6; k++) st.col[k * 6 + l] = sg[k];
+      }
+      continue;
+    }
+    const double* const p0 = mnlb_part(w, bw, s, l, 0);
+    const double* const p1 = mnlb_part(w, bw, s, l, 1);
+    double sa = 0., sb = 0.;
+    for (int q = tid; q < cnt; q += MICRO_TPB) {
+      sa += p0[q];
+      if (PHASE != 1) sb += p1[q];
+    }
+    micro_reduce2(sa, sb, sred);
+    if (tid != 0) continue;
+    if (PHASE == 1) {
+      c.pq = sa;
+      if (!(sa > 0.)) {  // no curvature left along p: the column ends unconverged
+        c.status = 2;
+        c.done = 1;
+      } else {
+        c.alpha = c.rz / sa;
+      }
+    } else if (PHASE == 2) {
+      c.its++;
+      if (sqrt(sb) / c.norm0 <= a.m.rtol) {
+        c.done = 1;
+      } else {
+        c.beta = sa / c.rz;
+        c.rz = sa;
+        if (!(c.its < a.m.max_it)) {
+          c.status = 2;
+          c.done = 1;
+        }
+      }
+    } else {
+      c.rz = sa;
+      c.pq = c.alpha = c.beta = 0.;
+      c.norm0 = sqrt(sb);
+      c.its = 0;
+      c.status = 0;
+      c.pad = 0;
+      c.done = 0;
+      if (c.norm0 == 0.) {
+        c.done = 1;  // the boundary values solve the column: no iteration
+      } else if (!(0 < a.m.max_it)) {
+        c.status = 2;
+        c.done = 1;
+      }
+    }
+    alldone = alldone && c.done;
+  }
+  if (tid != 0) return;
+  if (PHASE == 0) {
+    int bad = 0;
+    for (int l = 0; l < 6; l++) {
+      st.cgits += col[l].its;
+      bad = bad || col[l].status;
+    }
+    st.lc = 6;
+    if (bad) {
+      st.status = 2;
+    } else {
+      for (int t = 0; t < 36; t++) ctan[t * ngp + st.q] = 0.5 * (st.col[t] + st.col[(t % 6) * 6 + t / 6]);
+    }
+    mnlg_end(st, ngp, its_out, rn_out, fail);
+  } else {
+    st.stage = alldone ? MNLG_BTRANS : MNLG_BCG;
+  }
+}
+
+// x_l += alpha_l p_l, r_l -= alpha_l q_l, z_l = D^-1 r_l: one thread per dof, the block's r.z and z.z per column
+__global__ __launch_bounds__(MICRO_TPB) void k_mnlb_update(MicroNlArgs a, MnlGridWs w, MnlBlockWs bw) {
+  __shared__ double sred[2 * (MICRO_TPB / 64)];
+  const int s = blockIdx.y;
+  const MnlGridState& st = w.st[s];
+  const bool newton = st.stage == MNLG_CG;
+  if (!newton && st.stage != MNLG_BCG) return;
+  const MnlBlockCol* const col = bw.col + 6 * (size_t)s;
+  const int ncol = newton ? 1 : 6, cpw = 6 / (int)gridDim.z, l0 = (int)blockIdx.z * cpw, l1 = min(l0 + cpw, ncol);
+  if (l0 >= l1) return;  // the whole workgroup: grid z splits the six columns, a Newton CG has one
+  const int64_t ndof = 3 * (int64_t)a.m.n * a.m.n * a.m.n, d = (int64_t)blockIdx.x * MICRO_TPB + threadIdx.x;
+  const double* const sd = mnlg_vec(w, s, 5, ndof);
+#pragma unroll 1
+  for (int l = l0; l < l1; l++) {
+    if (!newton && col[l].done) continue;  // the whole workgroup
+    const double alpha = newton ? st.alpha : col[l].alpha;
+    double rz = 0., zz = 0.;
+    if (d < ndof) {
+      double* const sx = mnlb_vec(w, bw, s, l, 1, ndof);
+      double* const sr = mnlb_vec(w, bw, s, l, 2, ndof);
+      sx[d] += alpha * mnlb_vec(w, bw, s, l, 3, ndof)[d];
+      const double rr = sr[d] - alpha * mnlb_vec(w, bw, s, l, 4, ndof)[d], z = sd[d] * rr;
+      sr[d] = rr;
+      rz += rr * z;
+      zz += z * z;
+    }
+    micro_reduce2(rz, zz, sred);
+    if (threadIdx.x == 0) {
+      mnlb_part(w, bw, s, l, 0)[blockIdx.x] = rz;
+      mnlb_part(w, bw, s, l, 1)[blockIdx.x] = zz;
+    }
+  }
+}
+
+// p_l = z_l + beta_l p_l
+__global__ __launch_bounds__(MICRO_TPB) void k_mnlb_pupdate(MicroNlArgs a, MnlGridWs w, MnlBlockWs bw) {
+  const int s = blockIdx.y;
+  const MnlGridState& st = w.st[s];
+  const bool newton = st.stage == MNLG_CG;
+  if (!newton && st.stage != MNLG_BCG) return;
+  const MnlBlockCol* const col = bw.col + 6 * (size_t)s;
+  const int ncol = newton ? 1 : 6, cpw = 6 / (int)gridDim.z, l0 = (int)blockIdx.z * cpw, l1 = min(l0 + cpw, ncol);
+  if (l0 >= l1) return;  // the whole workgroup: grid z splits the six columns, a Newton CG has one
+  const int64_t ndof = 3 * (int64_t)a.m.n * a.m.n * a.m.n, d = (int64_t)blockIdx.x * MICRO_TPB + threadIdx.x;
+  if (d >= ndof) return;
+  const double* const sd = mnlg_vec(w, s, 5, ndof);
+#pragma unroll 1
+  for (int l = l0; l < l1; l++) {
+    if (!newton && col[l].done) continue;
+    double* const sp = mnlb_vec(w, bw, s, l, 3, ndof);
+    sp[d] = sd[d] * mnlb_vec(w, bw, s, l, 2, ndof)[d] + (newton ? st.beta : col[l].beta) * sp[d];
+  }
 }
 
 // One 3x3 block A(node g, node g+d) of the assembled matrix (MatSetValuesLocal(ADD) +
@@ -7688,6 +8128,61 @@ void launch_mnlg_iterate(Ctx& c, const MicroNlArgs& a, const MnlGridWs& w, int c
   hipLaunchKernelGGL(k_mnlg_scalar<2>, one, tpb, 0, c.stream, a, w, nvb, ngp, c.sig, c.ctan, c.ftrial, c.mnl_its, c.mnl_rn,
                      c.mnl_cnt);
   hipLaunchKernelGGL(k_mnlg_pupdate, dofs, tpb, 0, c.stream, a, w);
+}
+
+// option micro_nl_tangent 1: the block's regions follow mnlg_layout's
+MnlBlockWs mnlb_layout(double* base, int n, int64_t batch) {
+  MnlBlockWs bw{};
+  bw.vec = base + mnlg_ws_bytes(n, batch) / (int64_t)sizeof(double);
+  bw.sig = bw.vec + batch * (mnlb_vec_bytes(n) / (int64_t)sizeof(double));
+  bw.part = bw.sig + batch * (mnlb_sig_bytes(n) / (int64_t)sizeof(double));
+  bw.col = reinterpret_cast<MnlBlockCol*>(bw.part + batch * 6 * MNLB_NPART * mg_npart(n));
+  return bw;
+}
+
+// The grid's z splits a block's six columns over workgroups (6 / z columns each; the column selects
+// memory only).  The gather, the update and the p update always take one column per workgroup.  The
+// Gauss-point pass keeps the six in one workgroup, which reads the tangent data once for all of them,
+// when the tiles of the batch already give every compute unit a workgroup; below that its columns
+// go to six workgroups, which read the tangent data once each, as the sequential pass does.
+static int mnlb_gp_z(const Ctx& c, int nt, int cnt) { return (int64_t)nt * cnt >= c.ncu ? 1 : 6; }
+
+// twelve launches: the Newton five of launch_mnlg_transition (the fifth sends a converged solve to the
+// block) and its x = 0 | the six x_l | their stresses | r_l, p_l | norm0_l | the stresses of the six
+// solutions | the tangent.  A block whose columns all end at their start (no interior dof) is formed
+// by the last two of the same transition.
+void launch_mnlb_transition(Ctx& c, const MicroNlArgs& a, const MnlGridWs& w, const MnlBlockWs& bw, int cnt) {
+  const int64_t ngp = 8 * c.g.nelem;
+  const int nn = a.m.n * a.m.n * a.m.n, nt = w.ntile * w.ntile * w.ntile, nnb = (nn + MICRO_TPB - 1) / MICRO_TPB;
+  const dim3 tiles(nt, cnt), nodes(nnb, cnt), one(cnt), tpb(MICRO_TPB);
+  const dim3 tiles6(nt, cnt, 6), tilesgp(nt, cnt, mnlb_gp_z(c, nt, cnt));
+  hipLaunchKernelGGL(k_mnlg_prep<false>, nodes, tpb, 0, c.stream, a, w, ngp, c.eps, c.mnl_ufield);
+  hipLaunchKernelGGL(k_mnlg_gp<1>, tiles, tpb, 0, c.stream, a, w, c.mnl_pool);
+  hipLaunchKernelGGL(k_mnlg_diag, nodes, tpb, 0, c.stream, a, w, c.mnl_pool);
+  hipLaunchKernelGGL(k_mnlg_gather<true>, tiles, tpb, 0, c.stream, a, w, c.mnl_pool);
+  hipLaunchKernelGGL(k_mnlg_scalar<4>, one, tpb, 0, c.stream, a, w, nt, ngp, c.sig, c.ctan, c.ftrial, c.mnl_its,
+                     c.mnl_rn, c.mnl_cnt);
+  hipLaunchKernelGGL(k_mnlg_prep<true>, nodes, tpb, 0, c.stream, a, w, ngp, c.eps, c.mnl_ufield);
+  hipLaunchKernelGGL(k_mnlb_prep, nodes, tpb, 0, c.stream, a, w, bw);
+  hipLaunchKernelGGL(k_mnlb_gp<2>, tilesgp, tpb, 0, c.stream, a, w, bw, c.mnl_pool);
+  hipLaunchKernelGGL(k_mnlb_gather<true>, tiles6, tpb, 0, c.stream, a, w, bw, c.mnl_pool);
+  hipLaunchKernelGGL(k_mnlb_scalar<3>, one, tpb, 0, c.stream, a, w, bw, nt, ngp, c.ctan, c.mnl_its, c.mnl_rn, c.mnl_cnt);
+  hipLaunchKernelGGL(k_mnlb_gp<1>, tiles6, tpb, 0, c.stream, a, w, bw, c.mnl_pool);
+  hipLaunchKernelGGL(k_mnlb_scalar<0>, one, tpb, 0, c.stream, a, w, bw, nt, ngp, c.ctan, c.mnl_its, c.mnl_rn, c.mnl_cnt);
+}
+
+// the six launches of launch_mnlg_iterate, each over the columns of a block not done (a Newton CG: one column)
+void launch_mnlb_iterate(Ctx& c, const MicroNlArgs& a, const MnlGridWs& w, const MnlBlockWs& bw, int cnt) {
+  const int64_t ngp = 8 * c.g.nelem;
+  const int nt = w.ntile * w.ntile * w.ntile;
+  const int nvb = (int)((3 * (int64_t)a.m.n * a.m.n * a.m.n + MICRO_TPB - 1) / MICRO_TPB);
+  const dim3 tilesgp(nt, cnt, mnlb_gp_z(c, nt, cnt)), tiles(nt, cnt, 6), dofs(nvb, cnt, 6), one(cnt), tpb(MICRO_TPB);
+  hipLaunchKernelGGL(k_mnlb_gp<0>, tilesgp, tpb, 0, c.stream, a, w, bw, c.mnl_pool);
+  hipLaunchKernelGGL(k_mnlb_gather<false>, tiles, tpb, 0, c.stream, a, w, bw, c.mnl_pool);
+  hipLaunchKernelGGL(k_mnlb_scalar<1>, one, tpb, 0, c.stream, a, w, bw, nt, ngp, c.ctan, c.mnl_its, c.mnl_rn, c.mnl_cnt);
+  hipLaunchKernelGGL(k_mnlb_update, dofs, tpb, 0, c.stream, a, w, bw);
+  hipLaunchKernelGGL(k_mnlb_scalar<2>, one, tpb, 0, c.stream, a, w, bw, nvb, ngp, c.ctan, c.mnl_its, c.mnl_rn, c.mnl_cnt);
+  hipLaunchKernelGGL(k_mnlb_pupdate, dofs, tpb, 0, c.stream, a, w, bw);
 }
 
 void launch_mnl_commit(Ctx& c, const MicroNlArgs& a) {

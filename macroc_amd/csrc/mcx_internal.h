@@ -164,6 +164,31 @@ inline int64_t mnlg_ws_bytes(int n, int64_t batch) {
   return batch * ((int64_t)sizeof(double) * (MNLG_NVEC * ndof + MNLG_NPART * mg_npart(n)) + (int64_t)sizeof(MnlGridState));
 }
 
+// option micro_nl_tangent 1: the six tangent columns of a solve advance together, each
+// with its own CG record.  Column 0 keeps the solve's x, r, p, q and the slot's work stresses; the
+// columns 1 .. 5 have theirs behind the layout above, in this order: the vectors
+// ([batch][5][4][3 n^3]: x, r, p, q), the work stresses ([batch][5][6][8 (n-1)^3]), the partial sums
+// ([batch][6][MNLB_NPART][npart]) and the column records ([batch][6]).  Three more stages, which the
+// k_mnlg_* kernels of the sequential columns do not know and so pass by.
+constexpr int MNLB_NPART = 8;  // per column: 0, 1 the dot products; 2 .. 7 the stress sums
+enum { MNLG_BSTART = 4, MNLG_BCG = 5, MNLG_BTRANS = 6 };
+struct MnlBlockCol {
+  double rz, pq, alpha, beta, norm0;  // the column's CG
+  int its, done, status, pad;         // its iterations; ended; 0 converged / 2 not
+};
+struct MnlBlockWs {
+  double* vec;
+  double* sig;
+  double* part;
+  MnlBlockCol* col;
+};
+inline int64_t mnlb_vec_bytes(int n) { return (int64_t)sizeof(double) * 5 * 4 * 3 * n * n * n; }
+inline int64_t mnlb_sig_bytes(int n) { return (int64_t)sizeof(double) * 5 * 6 * 8 * (n - 1) * (n - 1) * (n - 1); }
+inline int64_t mnlb_ws_bytes(int n, int64_t batch) {  // what the block adds to mnlg_ws_bytes
+  return batch * (mnlb_vec_bytes(n) + mnlb_sig_bytes(n) + (int64_t)sizeof(double) * 6 * MNLB_NPART * mg_npart(n) +
+                  6 * (int64_t)sizeof(MnlBlockCol));
+}
+
 // -pc_type mg: geometric multigrid preconditioner of the macro CG, one rank.  Level 0
 // is the assembled matrix (launch_spmv, whatever its storage); a coarser level keeps its Galerkin
 // operator as plain stencil blocks, slot-major: value (nb, r, c) of node n at A[(nb*9 + r*3 + c) * nn + n].
@@ -565,6 +590,10 @@ struct Ctx {
   // MICRO_NMAX_NL_GRID; micro_mem is ignored, micro_mem_blocks > 0 replaces the solves per launch
   int mnl_solver = 0;
   int mnl_start = 0, mnl_ls = 0;  // options micro_nl_start, micro_nl_ls: the globalised Newton loop
+  // option micro_nl_tangent: 1 = solver 1 advances a point's six tangent columns together;
+  // mnl_col_its: [6][ngp] the columns' CG iterations of the points the last call solved that way (else 0)
+  int mnl_tangent = 0;
+  std::vector<int> mnl_col_its;
   int64_t mnl_slots_opt = 0;     // option micro_nl_slots (0: what fits 2 GiB, at most the local Gauss points)
   int64_t mnl_cap = 0, mnl_used = 0;
   double* mnl_ufield = nullptr;  // [6][3 n^3] unit-strain solutions
@@ -669,6 +698,10 @@ MnlGridWs mnlg_layout(double* base, int n, int64_t batch);
 void launch_mnlg_start(Ctx& c, const MnlGridWs& w, int base, int cnt);
 void launch_mnlg_transition(Ctx& c, const MicroNlArgs& a, const MnlGridWs& w, int cnt);  // CG ended -> next CG started
 void launch_mnlg_iterate(Ctx& c, const MicroNlArgs& a, const MnlGridWs& w, int cnt);     // one gated CG iteration
+// option micro_nl_tangent 1: the same two with the six columns as one block (bw behind w's layout)
+MnlBlockWs mnlb_layout(double* base, int n, int64_t batch);
+void launch_mnlb_transition(Ctx& c, const MicroNlArgs& a, const MnlGridWs& w, const MnlBlockWs& bw, int cnt);
+void launch_mnlb_iterate(Ctx& c, const MicroNlArgs& a, const MnlGridWs& w, const MnlBlockWs& bw, int cnt);
 void launch_mnl_commit(Ctx& c, const MicroNlArgs& a);  // new history -> committed history, used slots
 void launch_gather_matrix(Ctx& c);
 void launch_gather_matrix_sym(Ctx& c);

@@ -139,7 +139,8 @@ static int run(int argc, char** argv) {
   PRINTF("\nMacroC : A HPC for FE2 Multi-scale Simulations\n\n");
   void* ctx = NULL;
   CHK(mcx_init(&o, g_rank, g_size, g_size > 1 ? id : NULL, &ctx));
-  /* the flags without an mcx_opts field (-micro_mem, -micro_rtol, -micro_nl_slots, ...) */
+  /* the flags without an mcx_opts field (-micro_mem, -micro_rtol, -micro_nl_slots, -micro_nl_solver,
+     -micro_nl_start, -micro_nl_ls, -micro_nl_tangent, ...) */
   CHK(mcx_apply_args(ctx, argc - 1, (const char* const*)argv + 1));
   const char* micro_mem = "lds";
   int micro_grid = 0;    /* -micro_solver grid */

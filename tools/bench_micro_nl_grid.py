@@ -7,6 +7,7 @@ point) and by solver 1 (grid-wide), and the linear-shortcut test alone on a grid
     python tools/bench_micro_nl_grid.py --n 33 --solver 1 --points --linear 16
     python tools/bench_micro_nl_grid.py --n 10 16 --solver 1 --points 8 --start 0 1 --ls 0 5
     python tools/bench_micro_nl_grid.py --n 17 --solver 1 --seed 5 --amp 2e-3 --stages 1 1.5 --start 1 --ls 5
+    python tools/bench_micro_nl_grid.py --n 10 16 20 --solver 1 --points 8 256 --ka 1e7 --tangent seq block
 
 Sphere cells, the tests' load (seed 5; --amp scales it); --ka sets the matrix' hardening modulus (the
 cells' plain Newton gives up on resolved cells with the tests' 1e6, DESIGN §18).  Host clock between two mcx_synchronize;
@@ -14,6 +15,7 @@ the second call of each is reported (the first one allocates).  One JSON line pe
 --start / --ls list values of the options micro_nl_start / micro_nl_ls, every pair is
 measured in the same process; --stages lists load factors with a commit between them, the last one
 is the one timed.  A stage whose cells do not converge is reported with the message, not raised.
+--tangent lists values of the option micro_nl_tangent (seq, block), measured in the same process.
 """
 import argparse
 import json
@@ -67,6 +69,7 @@ def main():
     ap.add_argument("--stages", type=float, nargs="+", default=[1.0], help="load factors, a commit between them; the last is timed")
     ap.add_argument("--start", type=int, nargs="+", default=[0], help="option micro_nl_start")
     ap.add_argument("--ls", type=int, nargs="+", default=[0], help="option micro_nl_ls")
+    ap.add_argument("--tangent", nargs="+", default=["seq"], choices=["seq", "block"], help="option micro_nl_tangent")
     ap.add_argument("--poll", type=int, default=0, help="option micro_grid_poll (0: leave it alone)")
     ap.add_argument("--linear", type=int, default=0, help="nodes per edge of a macro grid below yield: the linear test alone")
     ap.add_argument("--root", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -77,11 +80,12 @@ def main():
 
     for n in a.n:
         for solver in a.solver:
-            for pts, start, ls in [(p, s, k) for p in a.points for s in a.start for k in a.ls]:
+            for pts, start, ls, tangent in [(p, s, k, t) for p in a.points for s in a.start for k in a.ls
+                                            for t in a.tangent]:
                 grid = GRIDS[pts]
                 u1 = field(grid, seed=a.seed, amp=a.amp)
                 rec = dict(tag=a.tag, what="micro_nl", n=n, solver=solver, points=pts, amp=a.amp, seed=a.seed, ka=a.ka,
-                           stages=a.stages, equal=a.equal, start=start, ls=ls)
+                           stages=a.stages, equal=a.equal, start=start, ls=ls, tangent=tangent)
                 with M.Macroc(argv_of(n, grid, a.ka, a.equal)) as m:
                     m.set_option("micro_mem", 1)
                     m.set_option("micro_nl_solver", solver)
@@ -91,6 +95,8 @@ def main():
                         m.set_option("micro_nl_start", start)
                     if ls:
                         m.set_option("micro_nl_ls", ls)
+                    if tangent == "block":
+                        m.set_option("micro_nl_tangent", 1)
                     m.set_option("micro_nl_slots", pts)
                     try:
                         for fac in a.stages[:-1]:
@@ -114,7 +120,7 @@ def main():
                                       first_ms=first * 1e3, ms=dt * 1e3, us_per_point=dt * 1e6 / max(solved, 1),
                                       newton_max=int(info["newton_its"].max()), newton=info["newton_its"].tolist()[:8],
                                       cg_mean=float(cg.mean()) if solved else 0.0,
-                                      cg_max=int(info["cg_its"].max()),
+                                      cg_max=int(info["cg_its"].max()), cg_sum=int(info["cg_its"].sum()),
                                       us_per_cg_it=dt * 1e6 / max(int(info["cg_its"].max()), 1),
                                       rejects=int(steps["ls_rejects"].sum()) if steps else 0,
                                       min_step=float(steps["min_step"][info["path"] > 0].min()) if steps and solved else 1.0,
