@@ -373,7 +373,16 @@ int mcx_micro_get_phase(void* ctx, unsigned char* phase, int64_t* n);
  * of 3 micro_n^3 doubles instead of 6 and five more sets of work stresses (5 x 6 x 8 (micro_n - 1)^3
  * doubles), which shrinks the batch of solves that share a launch above micro_n = 20; device_bytes
  * counts the workspace.  Solver 0 accepts the option without effect and keeps its sequential columns
- * (its LDS is full), as do other laws.  The value changes only while no history slot is in use. */
+ * (its LDS is full), as do other laws.  The value changes only while no history slot is in use.
+ * "micro_nl_apply" (-micro_nl_apply split|fused, 0 | 1; default 0; another number fails with code 1,
+ * another word with code 2): how solver 1 forms q = K_T p in a CG iteration (Newton's, the tangent
+ * columns', the block's).  0 takes two launches: a Gauss-point pass writes six work stresses per micro
+ * Gauss point into the slot, a node gather reads them back.  1 takes one: a workgroup marches the
+ * element layers of its tile of 8x8x8 nodes with one layer of stresses on chip and never writes the
+ * work stresses.  Every node's 64 terms are added in the same order, so q, p.q and with them every
+ * result and count are the same bits under both values.  Neither the workspace nor the slots follow
+ * the option: it may change at any time, also with history slots in use, and device_bytes is the
+ * same.  Solver 0 and other laws accept it without effect. */
 /* per Gauss point (mcx_get_gp_strain's order): path 0 = linear shortcut, 1 = solved; Newton
    iterations, CG iterations (Newton steps and tangent solves together) and the final relative
    Newton residual of the last mcx_homogenize.  Any pointer may be NULL. */
@@ -388,6 +397,10 @@ int mcx_micro_nl_get_steps(void* ctx, int* ls_rejects, double* min_step);
    iterations of each of the six tangent columns of the last mcx_homogenize where solver 1 ran them
    as a block; 0 for every other point.  Either pointer may be NULL. */
 int mcx_micro_nl_get_tangent(void* ctx, int* block, int* col_its);
+/* the option "micro_nl_apply" and the launches of the fused kernel that the last mcx_homogenize
+   enqueued: 0 under "micro_nl_apply" 0, under solver 0 and when no point was solved.  Either pointer
+   may be NULL. */
+int mcx_micro_nl_get_apply(void* ctx, int* fused, long long* launches);
 
 double mcx_get_displacement(void* ctx, int time_s);
 int mcx_zero_u(void* ctx);                 /* VecZeroEntries(u)  src/init.c:103 */
@@ -454,7 +467,7 @@ int mcx_set_timing(void* ctx, int on);
 int mcx_get_timing(void* ctx, mcx_timing* t);
 int mcx_synchronize(void* ctx);
 /* tuning knobs ("spmv_subl": lines per sub-slab of the SpMV sweep, 0 = whole XCD slab; "micro_rtol",
-   "micro_max_it", "micro_mem", "micro_solver", "micro_grid_poll": the micro cell's CG, -mat_law micro; "micro_nl_rtol", "micro_nl_max_it", "micro_nl_slots", "micro_nl_solver", "micro_nl_start", "micro_nl_ls", "micro_nl_tangent":
+   "micro_max_it", "micro_mem", "micro_solver", "micro_grid_poll": the micro cell's CG, -mat_law micro; "micro_nl_rtol", "micro_nl_max_it", "micro_nl_slots", "micro_nl_solver", "micro_nl_start", "micro_nl_ls", "micro_nl_tangent", "micro_nl_apply":
    -mat_law micro_nl) and a
    device-only SpMV timer (iters launches on the current search direction, HIP events) */
 int mcx_set_option(void* ctx, const char* name, double value);
@@ -462,10 +475,11 @@ int mcx_set_option(void* ctx, const char* name, double value);
    -micro_mem lds|device ("micro_mem" 0 | 1), -micro_solver cell|grid ("micro_solver" 0 | 1), -micro_nl_solver cell|grid ("micro_nl_solver" 0 | 1),
    -micro_nl_start zero|elastic ("micro_nl_start" 0 | 1), -micro_nl_ls K ("micro_nl_ls", an integer 0 .. 16),
    -micro_nl_tangent seq|block ("micro_nl_tangent" 0 | 1),
+   -micro_nl_apply split|fused ("micro_nl_apply" 0 | 1),
    -micro_rtol, -micro_max_it, -micro_nl_rtol, -micro_nl_max_it, -micro_nl_slots (each with a
    number), -pc_type jacobi|mg ("pc_type" 0 | 1), -pc_mg_levels N, -mg_levels_ksp_max_it k
    ("pc_mg_smooth"), -pc_mg_dist 0|1 ("pc_mg_dist"; give it before -pc_type), -pc_mg_precision
-   double|single ("pc_mg_precision" 0 | 1).  mcx_parse_args accepts these flags and checks -micro_mem's, -micro_solver's, -micro_nl_solver's, -micro_nl_start's, -micro_nl_ls's, -micro_nl_tangent's and -pc_mg_precision's word; call this after mcx_init with the same argv.  Other flags are skipped. */
+   double|single ("pc_mg_precision" 0 | 1).  mcx_parse_args accepts these flags and checks -micro_mem's, -micro_solver's, -micro_nl_solver's, -micro_nl_start's, -micro_nl_ls's, -micro_nl_tangent's, -micro_nl_apply's and -pc_mg_precision's word; call this after mcx_init with the same argv.  Other flags are skipped. */
 int mcx_apply_args(void* ctx, int argc, const char* const* argv);
 int mcx_time_spmv(void* ctx, int iters, double* avg_ms);
 

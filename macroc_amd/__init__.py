@@ -43,7 +43,7 @@ EXPORTS = [
     "mcx_micro_get_ctan", "mcx_micro_get_phase",
     "mcx_get_gp_ctan", "mcx_micro_nl_get_info", "mcx_micro_nl_get_pool", "mcx_micro_nl_get_steps", "mcx_apply_args",
     "mcx_pc_apply", "mcx_pc_mg_info", "mcx_pc_mg_dump_csr", "mcx_get_st_dma", "mcx_pc_mg_plan", "mcx_pc_mg_box",
-    "mcx_pc_mg_get_precision", "mcx_micro_nl_get_tangent",
+    "mcx_pc_mg_get_precision", "mcx_micro_nl_get_tangent", "mcx_micro_nl_get_apply",
 ]
 
 LAWS = {"elastic": 0, "plastic": 1, "external": 2, "micro": 3, "micro_nl": 4}
@@ -193,6 +193,7 @@ def lib():
     L.mcx_micro_nl_get_pool.argtypes = [vp, i64, i64, i64]
     L.mcx_micro_nl_get_steps.argtypes = [vp, ip, d]
     L.mcx_micro_nl_get_tangent.argtypes = [vp, ip, ip]
+    L.mcx_micro_nl_get_apply.argtypes = [vp, ip, C.POINTER(C.c_longlong)]
     for fn in ("mcx_set_gp_stress", "mcx_set_gp_ctan", "mcx_get_gp_strain", "mcx_get_gp_ctan"):
         getattr(L, fn).argtypes = [vp, d]
     L.mcx_micro_get_ctan.argtypes = [vp, d, C.POINTER(C.c_int), d]
@@ -513,6 +514,20 @@ class Macroc:
         _check(lib().mcx_micro_nl_get_tangent(self._ctx, None, its.ctypes.data_as(C.POINTER(C.c_int))),
                "mcx_micro_nl_get_tangent")
         return its
+
+    def micro_nl_apply(self):
+        """the option micro_nl_apply: 0 (split) a CG iteration of micro_nl_solver 1 forms q = K_T p by a
+        Gauss-point pass and a node gather, 1 (fused) in one launch that writes no work stresses."""
+        fused = C.c_int(0)
+        _check(lib().mcx_micro_nl_get_apply(self._ctx, C.byref(fused), None), "mcx_micro_nl_get_apply")
+        return fused.value
+
+    def micro_nl_apply_launches(self):
+        """launches of the fused kernel that the last homogenize enqueued (0 under micro_nl_apply 0,
+        under micro_nl_solver 0 and when no point was solved)."""
+        count = C.c_longlong(0)
+        _check(lib().mcx_micro_nl_get_apply(self._ctx, None, C.byref(count)), "mcx_micro_nl_get_apply")
+        return count.value
 
     # ---- the micro-scale cell (-mat_law micro)
     def micro_ctan(self):

@@ -401,7 +401,7 @@ using namespace mcx;
 static const char* const kApplyFlags[] = {"-micro_mem",     "-micro_rtol",      "-micro_max_it",  "-micro_nl_rtol",
                                           "-micro_nl_max_it", "-micro_nl_slots", "-micro_solver",
                                           "-micro_nl_solver", "-micro_nl_start",  "-micro_nl_ls",
-                                          "-micro_nl_tangent",
+                                          "-micro_nl_tangent", "-micro_nl_apply",
                                           "-pc_type",       "-pc_mg_levels",    "-mg_levels_ksp_max_it",
                                           "-pc_mg_dist",    "-pc_mg_precision"};
 static bool apply_flag(const char* k) {
@@ -559,6 +559,10 @@ int mcx_parse_args(mcx_opts* o, int argc, const char* const* argv) try {
       }
       if (!std::strcmp(k, "-micro_nl_tangent") && (!v || (std::strcmp(v, "seq") && std::strcmp(v, "block")))) {
         set_error(std::string("-micro_nl_tangent: seq or block, got ") + (v ? v : "(none)"));
+        return 2;
+      }
+      if (!std::strcmp(k, "-micro_nl_apply") && (!v || (std::strcmp(v, "split") && std::strcmp(v, "fused")))) {
+        set_error(std::string("-micro_nl_apply: split or fused, got ") + (v ? v : "(none)"));
         return 2;
       }
       if (!std::strcmp(k, "-pc_mg_precision") && (!v || (std::strcmp(v, "double") && std::strcmp(v, "single")))) {
@@ -744,6 +748,15 @@ int mcx_micro_nl_get_tangent(void* ctx, int* block, int* col_its) try {
         for (int l = 0; l < 6; l++)
           col_its[(e * 8 + gp) * 6 + l] = c.mnl_col_its.empty() ? 0 : c.mnl_col_its[(size_t)(l * ngp + gp * E + e)];
   }
+  return 0;
+} MCX_CATCH
+
+int mcx_micro_nl_get_apply(void* ctx, int* fused, long long* launches) try {
+  MCX_ENTRY();
+  GUARD(ctx);
+  CTX(ctx);
+  if (fused) *fused = c.mnl_apply;
+  if (launches) *launches = c.mnl_apply_launches;
   return 0;
 } MCX_CATCH
 
@@ -1132,6 +1145,7 @@ static int solve_mnl_grid(Ctx& c, const MicroNlArgs& a, int nsolve) {
 }
 
 static int micro_nl_homogenize(Ctx& c) {
+  c.mnl_apply_launches = 0;
   if (int rc = ensure_micro(c)) return rc;
   const MicroNlArgs a = mnl_args(c);
   const int64_t ngp = 8 * c.g.nelem, bytes = mnl_slot_bytes(c);
@@ -2419,6 +2433,15 @@ int mcx_set_option(void* ctx, const char* name, double value) try {
     if (micro_nl_grid(c) && c.micro_grid_ws) return micro_resize(c, &c.micro_grid_ws, &c.micro_grid_bytes, grid_ws_bytes(c));
     return 0;
   }
+  if (!std::strcmp(name, "micro_nl_apply")) {  // how solver 1 forms a CG iteration's q = K_T p
+    if (value != 0. && value != 1.) {
+      set_error("micro_nl_apply: 0 (split: the Gauss-point pass writes the work stresses, the node gather reads them) or 1 "
+                "(fused: micro_nl_solver 1 forms q = K_T p and p.q in one launch, no work stresses written)");
+      return 1;
+    }
+    c.mnl_apply = (int)value;  // neither the workspace nor the slots follow it: any time; solver 0 and the other laws: no effect
+    return 0;
+  }
   if (!std::strcmp(name, "pc_mg_dist")) {  // 1: pc_type 1 on a context with a communicator (the distributed hierarchy)
     if (value != 0. && value != 1.) {
       set_error("pc_mg_dist: 0 (pc_type mg on one rank only) or 1 (the hierarchy distributed over the ranks)");
@@ -2916,6 +2939,12 @@ int mcx_apply_args(void* ctx, int argc, const char* const* argv) try {
         return 2;
       }
       value = std::strcmp(v, "block") ? 0. : 1.;
+    } else if (!std::strcmp(k, "-micro_nl_apply")) {
+      if (std::strcmp(v, "split") && std::strcmp(v, "fused")) {
+        set_error(std::string("-micro_nl_apply: split or fused, got ") + v);
+        return 2;
+      }
+      value = std::strcmp(v, "fused") ? 0. : 1.;
     } else if (!std::strcmp(k, "-pc_mg_precision")) {
       if (std::strcmp(v, "double") && std::strcmp(v, "single")) {
         set_error(std::string("-pc_mg_precision: double or single, got ") + v);

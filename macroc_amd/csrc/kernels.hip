@@ -2197,6 +2197,147 @@ __global__ __launch_bounds__(MICRO_TPB) void k_mnlg_gather(MicroNlArgs a, MnlGri
   }
 }
 
+// ---------------------------------------------------------------------------- q = K_T p in one pass
+// option micro_nl_apply 1: k_mnlg_gp<0> and k_mnlg_gather<false> as one launch that never
+// writes the work stresses.  A workgroup owns k_mnlg_gather's tile of MG_T^3 nodes.  It stages the
+// (MG_T + 2)^3 nodes of p its (MG_T + 1)^3 elements touch (zero outside the cell, component-major) and
+// marches these elements' MG_T + 1 layers in ascending z.  Per layer: C_gp B p of the layer's
+// (MG_T + 1)^2 x 8 micro Gauss points into LDS (mnlg_strain's and mnl_Cmul's statements), a barrier,
+// then the layer's terms of mnl_gather_sig's sum: a node's elements ascend with z first, so element
+// layer e holds the last 32 of the 64 terms of node layer e (the node is the element's corner oz = 0)
+// and the first 32 of node layer e + 1 (oz = 1), each in mnl_gather_sig's order (oy = 1, 0; ox = 1, 0;
+// Gauss point 0 .. 7).  The sum of the open node layer waits in LDS for the next element layer, so
+// every y is today's chain of 64 additions.  A node's three components are independent chains: wave
+// 3 h + r adds component r of the first (h = 0) or the last (h = 1) 32 terms for the 64 nodes of a
+// layer, two waves idle.  The stress layer is [component][Gauss point][element], the element rows
+// padded to MNLA_ES: the lanes of a gathering wave read consecutive doubles.
+constexpr int MNLA_P = MG_T + 2, MNLA_P3 = MNLA_P * MNLA_P * MNLA_P;  // staged nodes
+constexpr int MNLA_E = MG_T + 1, MNLA_E2 = MNLA_E * MNLA_E;          // elements of a layer
+constexpr int MNLA_ES = 84;  // >= MNLA_E2, = 4 mod 16: the Gauss-point pass' 8-byte stores of 32 lanes are 2-way, their least
+
+// mnlg_strain on the (MG_T + 2)^3 staged nodes
+__device__ __forceinline__ void mnla_strain(const double* __restrict__ dn, const double* __restrict__ sv, int ei, int ej,
+                                            int ek, double (&eps)[6]) {
+  constexpr int P = MNLA_P, P3 = MNLA_P3;
+  double G[3][3] = {{0., 0., 0.}, {0., 0., 0.}, {0., 0., 0.}};  // G[r][d] = d u_r / d x_d
+#pragma unroll 1
+  for (int a = 0; a < 8; a++) {
+    const int hb = (ei + (a & 1)) + P * ((ej + (a >> 1 & 1)) + P * (ek + (a >> 2)));
+#pragma unroll
+    for (int r = 0; r < 3; r++)
+#pragma unroll
+      for (int d = 0; d < 3; d++) G[r][d] += dn[3 * a + d] * sv[r * P3 + hb];
+  }
+  eps[0] = G[0][0];
+  eps[1] = G[1][1];
+  eps[2] = G[2][2];
+  eps[3] = G[0][1] + G[1][0];
+  eps[4] = G[0][2] + G[2][0];
+  eps[5] = G[1][2] + G[2][1];
+}
+
+// the tile march: q = K_T p on the tile's interior nodes from the slot's tangent data, the tile's p.q
+// (k_mnlg_gather<false>'s sum and tree) to part[tile]; the whole workgroup calls it
+__device__ __forceinline__ void mnla_tile(const MicroNlArgs& a, int nt, int tile, const double* __restrict__ ws,
+                                          const double* __restrict__ sp, double* __restrict__ sq,
+                                          double* __restrict__ part) {
+  __shared__ double sv[3 * MNLA_P3];
+  __shared__ double ssig[6 * 8 * MNLA_ES];
+  __shared__ double sy[3 * MICRO_TPB];
+  __shared__ double sdn[8 * 24];
+  __shared__ double sred[2 * (MICRO_TPB / 64)];
+  const int tid = threadIdx.x;
+  const int n = a.m.n, ne = n - 1, nel = ne * ne * ne;
+  const size_t nmgp = 8 * (size_t)nel;
+  const int ox = MG_T * (tile % nt), oy = MG_T * ((tile / nt) % nt), oz = MG_T * (tile / (nt * nt));
+  const int i = ox + tid % MG_T, j = oy + (tid / MG_T) % MG_T, k = oz + tid / (MG_T * MG_T);
+  const bool in = i < n && j < n && k < n;
+  const bool bnd = i == 0 || j == 0 || k == 0 || i == ne || j == ne || k == ne;
+  const size_t nd = in ? (size_t)i + (size_t)n * ((size_t)j + (size_t)n * (size_t)k) : 0;
+  // a tile without an interior node (its nodes all on the boundary or outside the cell) has no element work
+  const bool work = max(ox, 1) < min(ox + MG_T, ne) && max(oy, 1) < min(oy + MG_T, ne) && max(oz, 1) < min(oz + MG_T, ne);
+  if (work) {  // the whole workgroup
+    const double detJ = 1. / (8. * (double)nel);
+    const double Gp[2] = {a.m.E[0] / (2. * (1. + a.m.nu[0])), a.m.E[1] / (2. * (1. + a.m.nu[1]))};
+    const double Kp[2] = {a.m.E[0] / (3. * (1. - 2. * a.m.nu[0])), a.m.E[1] / (3. * (1. - 2. * a.m.nu[1]))};
+    for (int t = tid; t < 8 * 24; t += MICRO_TPB) sdn[t] = mnl_dn(t, ne);
+    for (int h = tid; h < MNLA_P3; h += MICRO_TPB) {
+      const int gi = ox - 1 + h % MNLA_P, gj = oy - 1 + (h / MNLA_P) % MNLA_P, gk = oz - 1 + h / (MNLA_P * MNLA_P);
+      const bool hin = gi >= 0 && gj >= 0 && gk >= 0 && gi < n && gj < n && gk < n;
+      const size_t hd = hin ? (size_t)gi + (size_t)n * ((size_t)gj + (size_t)n * (size_t)gk) : 0;
+#pragma unroll
+      for (int r = 0; r < 3; r++) sv[r * MNLA_P3 + h] = hin ? sp[3 * hd + r] : 0.;
+    }
+    __syncthreads();
+    const int wv = tid >> 6, lane = tid & 63, half = wv / 3, r = wv - 3 * half;  // the gather's wave: wv < 6
+    const int li = lane % MG_T, lj = lane / MG_T, gi = ox + li, gj = oy + lj;
+    // component r of B_a^T sigma: dn[d0] s[r] + dn[d1] s[c1] + dn[d2] s[c2] (mnl_gather_sig's three lines)
+    const int d1 = r == 0 ? 1 : 0, d2 = r == 2 ? 1 : 2, c1 = r == 2 ? 4 : 3, c2 = r == 0 ? 4 : 5;
+#pragma unroll 1
+    for (int lz = 0; lz < MNLA_E; lz++) {
+      const int ek = oz - 1 + lz;
+      if (ek < 0 || ek >= ne) continue;  // the whole workgroup
+      for (int t = tid; t < 8 * MNLA_E2; t += MICRO_TPB) {
+        const int gp = t & 7, el = t >> 3, lx = el % MNLA_E, ly = el / MNLA_E, ei = ox - 1 + lx, ej = oy - 1 + ly;
+        if (ei < 0 || ej < 0 || ei >= ne || ej >= ne) continue;
+        const int ph = micro_phase(a.m.type, ne, ei, ej, ek);
+        const size_t mg = 8 * ((size_t)ei + (size_t)ne * ((size_t)ej + (size_t)ne * (size_t)ek)) + gp;
+        double ee[6], nv[6], sgm[6];
+        mnla_strain(sdn + 24 * gp, sv, lx, ly, lz, ee);
+        const double th = ws[(size_t)MNL_TAN * nmgp + mg], thb = ws[(size_t)(MNL_TAN + 1) * nmgp + mg];
+#pragma unroll
+        for (int b = 0; b < 6; b++) nv[b] = ws[(size_t)(MNL_TAN + 2 + b) * nmgp + mg];
+        mnl_Cmul(ph ? Gp[1] : Gp[0], ph ? Kp[1] : Kp[0], th, thb, nv, ee, sgm);
+#pragma unroll
+        for (int c = 0; c < 6; c++) ssig[(c * 8 + gp) * MNLA_ES + el] = sgm[c];
+      }
+      __syncthreads();
+      // half 0: node layer lz, the corner oz = 1 of this element layer, starts its sum; half 1: node layer
+      // lz - 1, the corner oz = 0, ends the sum the layer before began
+      const int lk = lz - half, gk = oz + lk;
+      if (wv < 6 && lk >= 0 && lk < MG_T && gi > 0 && gj > 0 && gk > 0 && gi < ne && gj < ne && gk < ne) {
+        double y = half ? sy[r * MICRO_TPB + MG_T * MG_T * lk + lane] : 0.;
+#pragma unroll 1
+        for (int qy = 1; qy >= 0; qy--)
+#pragma unroll 1
+          for (int qx = 1; qx >= 0; qx--) {
+            const int ca = qx + 2 * qy + 4 * (1 - half), el = (lj + 1 - qy) * MNLA_E + (li + 1 - qx);
+#pragma unroll
+            for (int gp = 0; gp < 8; gp++) {
+              const double* dn = sdn + 24 * gp + 3 * ca;
+              const double* s = ssig + gp * MNLA_ES + el;
+              y += (dn[r] * s[r * 8 * MNLA_ES] + dn[d1] * s[c1 * 8 * MNLA_ES] + dn[d2] * s[c2 * 8 * MNLA_ES]) * detJ;
+            }
+          }
+        sy[r * MICRO_TPB + MG_T * MG_T * lk + lane] = y;
+      }
+      __syncthreads();
+    }
+  }
+  double s0 = 0., s1 = 0.;
+  if (work && in && !bnd) {
+#pragma unroll
+    for (int r = 0; r < 3; r++) {
+      const double y = sy[r * MICRO_TPB + tid];
+      sq[3 * nd + r] = y;
+      s0 += sp[3 * nd + r] * y;
+    }
+  }
+  micro_reduce2(s0, s1, sred);
+  if (tid == 0) part[tile] = s0;
+}
+
+// a CG iteration's q = K_T p and the tiles' p.q of the sequential solves: k_mnlg_gp<0> + k_mnlg_gather<false>
+__global__ __launch_bounds__(MICRO_TPB, 4) void k_mnlg_apply(MicroNlArgs a, MnlGridWs w, const double* __restrict__ pool) {
+  const int s = blockIdx.y;
+  const MnlGridState& st = w.st[s];
+  if (st.stage != MNLG_CG) return;  // the whole workgroup
+  const int ne = a.m.n - 1;
+  const int64_t ndof = 3 * (int64_t)a.m.n * a.m.n * a.m.n;
+  mnla_tile(a, w.ntile, blockIdx.x, pool + (size_t)st.slot * MNL_WS * (8 * (size_t)ne * ne * ne), mnlg_vec(w, s, 3, ndof),
+            mnlg_vec(w, s, 4, ndof), mnlg_part(w, s, 0));
+}
+
 // a solve ends: what mcx_micro_nl_get_info reports; the only atomic is the integer count of failed cells
 __device__ __forceinline__ void mnlg_end(MnlGridState& st, int64_t ngp, int* __restrict__ its_out,
                                          double* __restrict__ rn_out, int* __restrict__ cnt) {
@@ -2615,6 +2756,22 @@ __global__ __launch_bounds__(MICRO_TPB) void k_mnlb_gather(MicroNlArgs a, MnlGri
       if (INIT) mnlb_part(w, bw, s, l, 1)[tile] = s1;
     }
   }
+}
+
+// option micro_nl_apply 1: k_mnlb_gp<0> + k_mnlb_gather<false> as one launch, mnla_tile on
+// the column's p, q and partial array; always one column per workgroup (grid z = 6), a column that is
+// done passes by, a Newton CG is column 0 alone.  The columns' work sets are not written.
+__global__ __launch_bounds__(MICRO_TPB, 4) void k_mnlb_apply(MicroNlArgs a, MnlGridWs w, MnlBlockWs bw,
+                                                             const double* __restrict__ pool) {
+  const int s = blockIdx.y, l = blockIdx.z;
+  const MnlGridState& st = w.st[s];
+  const bool newton = st.stage == MNLG_CG;
+  if (!newton && st.stage != MNLG_BCG) return;  // the whole workgroup
+  if (newton ? l > 0 : bw.col[6 * (size_t)s + l].done) return;  // the whole workgroup
+  const int ne = a.m.n - 1;
+  const int64_t ndof = 3 * (int64_t)a.m.n * a.m.n * a.m.n;
+  mnla_tile(a, w.ntile, blockIdx.x, pool + (size_t)st.slot * MNL_WS * (8 * (size_t)ne * ne * ne), mnlb_vec(w, bw, s, l, 3, ndof),
+            mnlb_vec(w, bw, s, l, 4, ndof), mnlb_part(w, bw, s, l, 0));
 }
 
 // The scalar steps of the block, one workgroup per solve, column after column: each column's partials
@@ -8115,13 +8272,19 @@ void launch_mnlg_transition(Ctx& c, const MicroNlArgs& a, const MnlGridWs& w, in
 }
 
 // six launches: stresses of p | q = K_T p, p.q | pq, alpha | x, r, z | its, rel, beta | p
+// (option micro_nl_apply 1: the first two are one)
 void launch_mnlg_iterate(Ctx& c, const MicroNlArgs& a, const MnlGridWs& w, int cnt) {
   const int64_t ngp = 8 * c.g.nelem;
   const int nt = w.ntile * w.ntile * w.ntile;
   const int nvb = (int)((3 * (int64_t)a.m.n * a.m.n * a.m.n + MICRO_TPB - 1) / MICRO_TPB);
   const dim3 tiles(nt, cnt), dofs(nvb, cnt), one(cnt), tpb(MICRO_TPB);
-  hipLaunchKernelGGL(k_mnlg_gp<0>, tiles, tpb, 0, c.stream, a, w, c.mnl_pool);
-  hipLaunchKernelGGL(k_mnlg_gather<false>, tiles, tpb, 0, c.stream, a, w, c.mnl_pool);
+  if (c.mnl_apply) {  // option micro_nl_apply 1: the two as one launch, five in all
+    hipLaunchKernelGGL(k_mnlg_apply, tiles, tpb, 0, c.stream, a, w, c.mnl_pool);
+    c.mnl_apply_launches++;
+  } else {
+    hipLaunchKernelGGL(k_mnlg_gp<0>, tiles, tpb, 0, c.stream, a, w, c.mnl_pool);
+    hipLaunchKernelGGL(k_mnlg_gather<false>, tiles, tpb, 0, c.stream, a, w, c.mnl_pool);
+  }
   hipLaunchKernelGGL(k_mnlg_scalar<1>, one, tpb, 0, c.stream, a, w, nt, ngp, c.sig, c.ctan, c.ftrial, c.mnl_its, c.mnl_rn,
                      c.mnl_cnt);
   hipLaunchKernelGGL(k_mnlg_update, dofs, tpb, 0, c.stream, a, w);
@@ -8177,8 +8340,13 @@ void launch_mnlb_iterate(Ctx& c, const MicroNlArgs& a, const MnlGridWs& w, const
   const int nt = w.ntile * w.ntile * w.ntile;
   const int nvb = (int)((3 * (int64_t)a.m.n * a.m.n * a.m.n + MICRO_TPB - 1) / MICRO_TPB);
   const dim3 tilesgp(nt, cnt, mnlb_gp_z(c, nt, cnt)), tiles(nt, cnt, 6), dofs(nvb, cnt, 6), one(cnt), tpb(MICRO_TPB);
-  hipLaunchKernelGGL(k_mnlb_gp<0>, tilesgp, tpb, 0, c.stream, a, w, bw, c.mnl_pool);
-  hipLaunchKernelGGL(k_mnlb_gather<false>, tiles, tpb, 0, c.stream, a, w, bw, c.mnl_pool);
+  if (c.mnl_apply) {  // option micro_nl_apply 1: the two as one launch, one column per workgroup
+    hipLaunchKernelGGL(k_mnlb_apply, tiles, tpb, 0, c.stream, a, w, bw, c.mnl_pool);
+    c.mnl_apply_launches++;
+  } else {
+    hipLaunchKernelGGL(k_mnlb_gp<0>, tilesgp, tpb, 0, c.stream, a, w, bw, c.mnl_pool);
+    hipLaunchKernelGGL(k_mnlb_gather<false>, tiles, tpb, 0, c.stream, a, w, bw, c.mnl_pool);
+  }
   hipLaunchKernelGGL(k_mnlb_scalar<1>, one, tpb, 0, c.stream, a, w, bw, nt, ngp, c.ctan, c.mnl_its, c.mnl_rn, c.mnl_cnt);
   hipLaunchKernelGGL(k_mnlb_update, dofs, tpb, 0, c.stream, a, w, bw);
   hipLaunchKernelGGL(k_mnlb_scalar<2>, one, tpb, 0, c.stream, a, w, bw, nvb, ngp, c.ctan, c.mnl_its, c.mnl_rn, c.mnl_cnt);

@@ -594,6 +594,10 @@ struct Ctx {
   // mnl_col_its: [6][ngp] the columns' CG iterations of the points the last call solved that way (else 0)
   int mnl_tangent = 0;
   std::vector<int> mnl_col_its;
+  // option micro_nl_apply: 1 = solver 1 forms a CG iteration's q = K_T p and p.q in one launch
+  // (k_mnlg_apply / k_mnlb_apply) that never writes the work stresses; the launches of the last mcx_homogenize
+  int mnl_apply = 0;
+  long long mnl_apply_launches = 0;
   int64_t mnl_slots_opt = 0;     // option micro_nl_slots (0: what fits 2 GiB, at most the local Gauss points)
   int64_t mnl_cap = 0, mnl_used = 0;
   double* mnl_ufield = nullptr;  // [6][3 n^3] unit-strain solutions

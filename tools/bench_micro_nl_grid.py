@@ -8,6 +8,7 @@ point) and by solver 1 (grid-wide), and the linear-shortcut test alone on a grid
     python tools/bench_micro_nl_grid.py --n 10 16 --solver 1 --points 8 --start 0 1 --ls 0 5
     python tools/bench_micro_nl_grid.py --n 17 --solver 1 --seed 5 --amp 2e-3 --stages 1 1.5 --start 1 --ls 5
     python tools/bench_micro_nl_grid.py --n 10 16 20 --solver 1 --points 8 256 --ka 1e7 --tangent seq block
+    python tools/bench_micro_nl_grid.py --n 10 16 20 32 --solver 1 --points 8 --ka 1e7 --apply split fused
 
 Sphere cells, the tests' load (seed 5; --amp scales it); --ka sets the matrix' hardening modulus (the
 cells' plain Newton gives up on resolved cells with the tests' 1e6, DESIGN §18).  Host clock between two mcx_synchronize;
@@ -16,6 +17,7 @@ the second call of each is reported (the first one allocates).  One JSON line pe
 measured in the same process; --stages lists load factors with a commit between them, the last one
 is the one timed.  A stage whose cells do not converge is reported with the message, not raised.
 --tangent lists values of the option micro_nl_tangent (seq, block), measured in the same process.
+--apply lists values of the option micro_nl_apply (split, fused), measured in the same process.
 """
 import argparse
 import json
@@ -70,6 +72,7 @@ def main():
     ap.add_argument("--start", type=int, nargs="+", default=[0], help="option micro_nl_start")
     ap.add_argument("--ls", type=int, nargs="+", default=[0], help="option micro_nl_ls")
     ap.add_argument("--tangent", nargs="+", default=["seq"], choices=["seq", "block"], help="option micro_nl_tangent")
+    ap.add_argument("--apply", nargs="+", default=["split"], choices=["split", "fused"], help="option micro_nl_apply")
     ap.add_argument("--poll", type=int, default=0, help="option micro_grid_poll (0: leave it alone)")
     ap.add_argument("--linear", type=int, default=0, help="nodes per edge of a macro grid below yield: the linear test alone")
     ap.add_argument("--root", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -80,12 +83,12 @@ def main():
 
     for n in a.n:
         for solver in a.solver:
-            for pts, start, ls, tangent in [(p, s, k, t) for p in a.points for s in a.start for k in a.ls
-                                            for t in a.tangent]:
+            for pts, start, ls, tangent, apply in [(p, s, k, t, f) for p in a.points for s in a.start for k in a.ls
+                                                   for t in a.tangent for f in a.apply]:
                 grid = GRIDS[pts]
                 u1 = field(grid, seed=a.seed, amp=a.amp)
                 rec = dict(tag=a.tag, what="micro_nl", n=n, solver=solver, points=pts, amp=a.amp, seed=a.seed, ka=a.ka,
-                           stages=a.stages, equal=a.equal, start=start, ls=ls, tangent=tangent)
+                           stages=a.stages, equal=a.equal, start=start, ls=ls, tangent=tangent, apply=apply)
                 with M.Macroc(argv_of(n, grid, a.ka, a.equal)) as m:
                     m.set_option("micro_mem", 1)
                     m.set_option("micro_nl_solver", solver)
@@ -97,6 +100,8 @@ def main():
                         m.set_option("micro_nl_ls", ls)
                     if tangent == "block":
                         m.set_option("micro_nl_tangent", 1)
+                    if apply == "fused":
+                        m.set_option("micro_nl_apply", 1)
                     m.set_option("micro_nl_slots", pts)
                     try:
                         for fac in a.stages[:-1]:
@@ -114,6 +119,7 @@ def main():
                     info = m.micro_nl_info()
                     steps = m.micro_nl_steps() if hasattr(m, "micro_nl_steps") else None
                     dev = m.get_info()["device_bytes"]
+                    fused = m.micro_nl_apply_launches() if hasattr(m, "micro_nl_apply_launches") else 0
                 solved = int(info["path"].sum())
                 cg = info["cg_its"][info["path"] > 0]
                 print(json.dumps(dict(rec, converged=True, solved=solved,
@@ -124,7 +130,7 @@ def main():
                                       us_per_cg_it=dt * 1e6 / max(int(info["cg_its"].max()), 1),
                                       rejects=int(steps["ls_rejects"].sum()) if steps else 0,
                                       min_step=float(steps["min_step"][info["path"] > 0].min()) if steps and solved else 1.0,
-                                      device_gb=dev / 1e9)), flush=True)
+                                      apply_launches=fused, device_gb=dev / 1e9)), flush=True)
             if a.linear:
                 grid = (a.linear,) * 3
                 with M.Macroc(argv_of(n, grid, a.ka, a.equal)) as m:
