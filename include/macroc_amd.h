@@ -382,7 +382,21 @@ int mcx_micro_get_phase(void* ctx, unsigned char* phase, int64_t* n);
  * work stresses.  Every node's 64 terms are added in the same order, so q, p.q and with them every
  * result and count are the same bits under both values.  Neither the workspace nor the slots follow
  * the option: it may change at any time, also with history slots in use, and device_bytes is the
- * same.  Solver 0 and other laws accept it without effect. */
+ * same.  Solver 0 and other laws accept it without effect.
+ * "micro_nl_warm" (-micro_nl_warm off|on, 0 | 1; default 0; another number fails with code 1, another
+ * word with code 2): 1 lets solver 1 start a slotted point from its slot's warm record, the interior
+ * field u_w, the six tangent columns W_l and the strain eps_w of the slot's last converged solve.  The
+ * first state pass stays at the zero interior (D and the first norm keep their bits, so both stops mean
+ * what they mean under every other setting); then the interior takes u_w + sum_l (eps - eps_w)_l W_l
+ * instead of what "micro_nl_start" says, and tangent column l starts from W_l and ends with no
+ * iteration if that already meets micro_rtol.  A point without a valid record (the first solve of its
+ * slot, or after a failed solve) follows "micro_nl_start" bit for bit.  The records live in one
+ * allocation of 7 x 24 micro_n^3 + 64 bytes per slot, counted in device_bytes, which exists while the
+ * option is 1 and a pool exists; it is allocated with every record invalid (also when the option is
+ * switched on with slots in use or "micro_nl_slots" changes) and freed when the option returns to 0.
+ * mcx_update_vars does not touch it.  The results depend on the strain, the committed history, the
+ * options and the record's contents only.  The option may change at any time.  Solver 0 and other laws
+ * accept it without effect. */
 /* per Gauss point (mcx_get_gp_strain's order): path 0 = linear shortcut, 1 = solved; Newton
    iterations, CG iterations (Newton steps and tangent solves together) and the final relative
    Newton residual of the last mcx_homogenize.  Any pointer may be NULL. */
@@ -401,6 +415,10 @@ int mcx_micro_nl_get_tangent(void* ctx, int* block, int* col_its);
    enqueued: 0 under "micro_nl_apply" 0, under solver 0 and when no point was solved.  Either pointer
    may be NULL. */
 int mcx_micro_nl_get_apply(void* ctx, int* fused, long long* launches);
+/* the option "micro_nl_warm" and, per Gauss point (the same order; used[8 nelem]) of the last
+   mcx_homogenize: 0 not solved (the linear shortcut, micro_n = 2), 1 solved without a valid warm
+   record, 2 solved from its record.  Either pointer may be NULL. */
+int mcx_micro_nl_get_warm(void* ctx, int* option, int* used);
 
 double mcx_get_displacement(void* ctx, int time_s);
 int mcx_zero_u(void* ctx);                 /* VecZeroEntries(u)  src/init.c:103 */
@@ -467,7 +485,7 @@ int mcx_set_timing(void* ctx, int on);
 int mcx_get_timing(void* ctx, mcx_timing* t);
 int mcx_synchronize(void* ctx);
 /* tuning knobs ("spmv_subl": lines per sub-slab of the SpMV sweep, 0 = whole XCD slab; "micro_rtol",
-   "micro_max_it", "micro_mem", "micro_solver", "micro_grid_poll": the micro cell's CG, -mat_law micro; "micro_nl_rtol", "micro_nl_max_it", "micro_nl_slots", "micro_nl_solver", "micro_nl_start", "micro_nl_ls", "micro_nl_tangent", "micro_nl_apply":
+   "micro_max_it", "micro_mem", "micro_solver", "micro_grid_poll": the micro cell's CG, -mat_law micro; "micro_nl_rtol", "micro_nl_max_it", "micro_nl_slots", "micro_nl_solver", "micro_nl_start", "micro_nl_ls", "micro_nl_tangent", "micro_nl_apply", "micro_nl_warm":
    -mat_law micro_nl) and a
    device-only SpMV timer (iters launches on the current search direction, HIP events) */
 int mcx_set_option(void* ctx, const char* name, double value);
@@ -476,10 +494,11 @@ int mcx_set_option(void* ctx, const char* name, double value);
    -micro_nl_start zero|elastic ("micro_nl_start" 0 | 1), -micro_nl_ls K ("micro_nl_ls", an integer 0 .. 16),
    -micro_nl_tangent seq|block ("micro_nl_tangent" 0 | 1),
    -micro_nl_apply split|fused ("micro_nl_apply" 0 | 1),
+   -micro_nl_warm off|on ("micro_nl_warm" 0 | 1),
    -micro_rtol, -micro_max_it, -micro_nl_rtol, -micro_nl_max_it, -micro_nl_slots (each with a
    number), -pc_type jacobi|mg ("pc_type" 0 | 1), -pc_mg_levels N, -mg_levels_ksp_max_it k
    ("pc_mg_smooth"), -pc_mg_dist 0|1 ("pc_mg_dist"; give it before -pc_type), -pc_mg_precision
-   double|single ("pc_mg_precision" 0 | 1).  mcx_parse_args accepts these flags and checks -micro_mem's, -micro_solver's, -micro_nl_solver's, -micro_nl_start's, -micro_nl_ls's, -micro_nl_tangent's, -micro_nl_apply's and -pc_mg_precision's word; call this after mcx_init with the same argv.  Other flags are skipped. */
+   double|single ("pc_mg_precision" 0 | 1).  mcx_parse_args accepts these flags and checks -micro_mem's, -micro_solver's, -micro_nl_solver's, -micro_nl_start's, -micro_nl_ls's, -micro_nl_tangent's, -micro_nl_apply's, -micro_nl_warm's and -pc_mg_precision's word; call this after mcx_init with the same argv.  Other flags are skipped. */
 int mcx_apply_args(void* ctx, int argc, const char* const* argv);
 int mcx_time_spmv(void* ctx, int iters, double* avg_ms);
 

@@ -43,7 +43,7 @@ EXPORTS = [
     "mcx_micro_get_ctan", "mcx_micro_get_phase",
     "mcx_get_gp_ctan", "mcx_micro_nl_get_info", "mcx_micro_nl_get_pool", "mcx_micro_nl_get_steps", "mcx_apply_args",
     "mcx_pc_apply", "mcx_pc_mg_info", "mcx_pc_mg_dump_csr", "mcx_get_st_dma", "mcx_pc_mg_plan", "mcx_pc_mg_box",
-    "mcx_pc_mg_get_precision", "mcx_micro_nl_get_tangent", "mcx_micro_nl_get_apply",
+    "mcx_pc_mg_get_precision", "mcx_micro_nl_get_tangent", "mcx_micro_nl_get_apply", "mcx_micro_nl_get_warm",
 ]
 
 LAWS = {"elastic": 0, "plastic": 1, "external": 2, "micro": 3, "micro_nl": 4}
@@ -194,6 +194,7 @@ def lib():
     L.mcx_micro_nl_get_steps.argtypes = [vp, ip, d]
     L.mcx_micro_nl_get_tangent.argtypes = [vp, ip, ip]
     L.mcx_micro_nl_get_apply.argtypes = [vp, ip, C.POINTER(C.c_longlong)]
+    L.mcx_micro_nl_get_warm.argtypes = [vp, ip, ip]
     for fn in ("mcx_set_gp_stress", "mcx_set_gp_ctan", "mcx_get_gp_strain", "mcx_get_gp_ctan"):
         getattr(L, fn).argtypes = [vp, d]
     L.mcx_micro_get_ctan.argtypes = [vp, d, C.POINTER(C.c_int), d]
@@ -528,6 +529,21 @@ class Macroc:
         count = C.c_longlong(0)
         _check(lib().mcx_micro_nl_get_apply(self._ctx, None, C.byref(count)), "mcx_micro_nl_get_apply")
         return count.value
+
+    def micro_nl_warm(self):
+        """[ngp] (gpi order), of the last homogenize: 0 the point was not solved (linear shortcut,
+        micro_n = 2), 1 solved without a valid warm record, 2 solved from its slot's warm record
+        (option micro_nl_warm 1 under micro_nl_solver 1)."""
+        used = np.zeros(self.ngp, np.int32)
+        _check(lib().mcx_micro_nl_get_warm(self._ctx, None, used.ctypes.data_as(C.POINTER(C.c_int))),
+               "mcx_micro_nl_get_warm")
+        return used
+
+    def micro_nl_warm_option(self):
+        """the option micro_nl_warm: 0 (off) or 1 (on)."""
+        opt = C.c_int(0)
+        _check(lib().mcx_micro_nl_get_warm(self._ctx, C.byref(opt), None), "mcx_micro_nl_get_warm")
+        return opt.value
 
     # ---- the micro-scale cell (-mat_law micro)
     def micro_ctan(self):

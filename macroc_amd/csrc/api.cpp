@@ -99,7 +99,7 @@ static int free_ctx(Ctx* c) {
   if (c->comm_stream) (void)hipStreamSynchronize(c->comm_stream);
   if (c->x_stream) (void)hipStreamSynchronize(c->x_stream);
   if (c->f_stream) (void)hipStreamSynchronize(c->f_stream);
-  void* ptrs[] = {c->micro_out, c->micro_ws, c->micro_grid_ws, c->mnl_ws, c->mnl_ufield, c->mnl_conc, c->mnl_slot, c->mnl_list, c->mnl_cnt, c->mnl_its, c->mnl_rn, c->mnl_pool, c->hist_old, c->hist_new, c->ftrial, c->b, c->du, c->r, c->z, c->w, c->jix, c->jdd, c->V, c->U, c->D, c->d_mask, c->vi_idx, c->wd, c->vi_dict, c->vi_keys, c->vi_slot, c->vi_ctl, c->vi_bdict, c->eps, c->sig, c->ctan, c->Ke,
+  void* ptrs[] = {c->micro_out, c->micro_ws, c->micro_grid_ws, c->mnl_ws, c->mnl_ufield, c->mnl_conc, c->mnl_slot, c->mnl_list, c->mnl_cnt, c->mnl_its, c->mnl_rn, c->mnl_pool, c->mnl_warm_store, c->hist_old, c->hist_new, c->ftrial, c->b, c->du, c->r, c->z, c->w, c->jix, c->jdd, c->V, c->U, c->D, c->d_mask, c->vi_idx, c->wd, c->vi_dict, c->vi_keys, c->vi_slot, c->vi_ctl, c->vi_bdict, c->eps, c->sig, c->ctan, c->Ke,
                   c->vib_keys, c->vib_ctl, c->vib_pos, c->ke_uni, c->xdone, c->esc_node, c->esc_res, c->esc_slot, c->elem_plain, c->cref, c->vi_xslot,
                   c->vi_xlist, c->vi_xcnt, c->vi_exc, c->st_coef, c->st_ids, c->st_slot, c->st_list, c->st_cnt, c->st_mask,
                   c->partials, c->red, c->red_loc, c->cg, c->hist, c->tmp, c->halo.d_send_idx,
@@ -401,7 +401,7 @@ using namespace mcx;
 static const char* const kApplyFlags[] = {"-micro_mem",     "-micro_rtol",      "-micro_max_it",  "-micro_nl_rtol",
                                           "-micro_nl_max_it", "-micro_nl_slots", "-micro_solver",
                                           "-micro_nl_solver", "-micro_nl_start",  "-micro_nl_ls",
-                                          "-micro_nl_tangent", "-micro_nl_apply",
+                                          "-micro_nl_tangent", "-micro_nl_apply", "-micro_nl_warm",
                                           "-pc_type",       "-pc_mg_levels",    "-mg_levels_ksp_max_it",
                                           "-pc_mg_dist",    "-pc_mg_precision"};
 static bool apply_flag(const char* k) {
@@ -563,6 +563,10 @@ int mcx_parse_args(mcx_opts* o, int argc, const char* const* argv) try {
       }
       if (!std::strcmp(k, "-micro_nl_apply") && (!v || (std::strcmp(v, "split") && std::strcmp(v, "fused")))) {
         set_error(std::string("-micro_nl_apply: split or fused, got ") + (v ? v : "(none)"));
+        return 2;
+      }
+      if (!std::strcmp(k, "-micro_nl_warm") && (!v || (std::strcmp(v, "off") && std::strcmp(v, "on")))) {
+        set_error(std::string("-micro_nl_warm: off or on, got ") + (v ? v : "(none)"));
         return 2;
       }
       if (!std::strcmp(k, "-pc_mg_precision") && (!v || (std::strcmp(v, "double") && std::strcmp(v, "single")))) {
@@ -757,6 +761,25 @@ int mcx_micro_nl_get_apply(void* ctx, int* fused, long long* launches) try {
   CTX(ctx);
   if (fused) *fused = c.mnl_apply;
   if (launches) *launches = c.mnl_apply_launches;
+  return 0;
+} MCX_CATCH
+
+int mcx_micro_nl_get_warm(void* ctx, int* option, int* used) try {
+  MCX_ENTRY();
+  GUARD(ctx);
+  CTX(ctx);
+  if (option) *option = c.mnl_warm;
+  if (used) {  // [8 nelem], Gauss points in the order of mcx_micro_nl_get_info
+    const int64_t E = c.g.nelem, ngp = 8 * E;
+    for (int64_t q = 0; q < ngp; q++) used[q] = 0;
+    if (c.mat.law == MCX_LAW_MICRO_NL && c.mnl_last_nsolve > 0 && c.mnl_list && c.micro.n > 2) {
+      std::vector<int> list((size_t)c.mnl_last_nsolve);
+      MCX_HIP(hipStreamSynchronize(c.stream));
+      MCX_HIP(hipMemcpy(list.data(), c.mnl_list, sizeof(int) * list.size(), hipMemcpyDeviceToHost));
+      for (int q : list)
+        used[((int64_t)q % E) * 8 + q / E] = 1 + (c.mnl_warm_hit.empty() ? 0 : (int)c.mnl_warm_hit[(size_t)q]);
+    }
+  }
   return 0;
 } MCX_CATCH
 
@@ -1081,6 +1104,17 @@ static int64_t mnl_slot_bytes(const Ctx& c) {
   return (int64_t)sizeof(double) * MNL_WS * 8 * ne * ne * ne;
 }
 
+// option micro_nl_warm: the warm store follows the option, the solver and the pool: mnl_cap
+// records, all invalid, when it is (re)allocated; a change of micro_nl_slots therefore invalidates them
+static int mnl_warm_resize(Ctx& c) {
+  const bool on = c.mnl_warm && micro_nl_grid(c) && c.mnl_pool && c.micro.n > 2;  // n = 2: no interior dof, nothing to keep
+  const int64_t want = on ? c.mnl_cap * mnl_warm_bytes(c.micro.n) : 0;
+  if (want == c.mnl_warm_store_bytes) return 0;
+  if (int rc = micro_resize(c, &c.mnl_warm_store, &c.mnl_warm_store_bytes, want)) return rc;
+  if (want > 0) MCX_HIP(hipMemsetAsync(c.mnl_warm_store, 0, (size_t)want, c.stream));
+  return 0;
+}
+
 // option micro_nl_solver 1: the nsolve listed points, mnl_grid_batch at a time, as launches
 // over the whole device.  Per batch the host enqueues one transition (a CG has ended or not begun:
 // the next Newton step, the next tangent column or the end) and up to micro_grid_poll gated CG
@@ -1094,7 +1128,12 @@ static int64_t mnl_slot_bytes(const Ctx& c) {
 static int solve_mnl_grid(Ctx& c, const MicroNlArgs& a, int nsolve) {
   const int64_t batch = mnl_grid_batch(c);
   if (int rc = micro_resize(c, &c.micro_grid_ws, &c.micro_grid_bytes, grid_ws_bytes(c))) return rc;
-  const MnlGridWs w = mnlg_layout(c.micro_grid_ws, a.m.n, batch);
+  MnlGridWs w = mnlg_layout(c.micro_grid_ws, a.m.n, batch);
+  if (c.mnl_warm_store) {  // option micro_nl_warm 1: [mnl_cap][7][3 n^3] fields, then [mnl_cap] headers
+    w.warm = c.mnl_warm_store;
+    w.whdr = reinterpret_cast<MnlWarmHdr*>(c.mnl_warm_store + c.mnl_cap * 7 * 3 * (int64_t)a.m.n * a.m.n * a.m.n);
+    c.mnl_warm_hit.assign((size_t)(8 * c.g.nelem), 0);
+  }
   const bool block = mnl_block(c);  // option micro_nl_tangent 1: the six columns of a solve as one block
   const MnlBlockWs bw = block ? mnlb_layout(c.micro_grid_ws, a.m.n, batch) : MnlBlockWs{};
   std::vector<MnlBlockCol> hc(block ? (size_t)batch * 6 : 0);
@@ -1102,7 +1141,7 @@ static int solve_mnl_grid(Ctx& c, const MicroNlArgs& a, int nsolve) {
   // a solve has at most nl_max_it + 1 state passes and six columns, each CG at most max_it iterations
   // (and, globalised, one more pass for the predictor and up to nl_ls more per step)
   const int64_t max_rounds = (int64_t)((a.nl_max_it + 1) * (a.nl_ls + 1) + 8) * ((int64_t)(std::max(a.m.max_it, 1) + per - 1) / per + 1);
-  const bool globalised = a.nl_start || a.nl_ls > 0;
+  const bool globalised = a.nl_start || a.nl_ls > 0 || w.warm;  // the warm predictor is a second state pass too
   std::vector<MnlGridState> h((size_t)batch);
   for (int base = 0; base < nsolve; base += (int)batch) {
     const int cnt = (int)std::min<int64_t>(batch, nsolve - base);
@@ -1133,6 +1172,8 @@ static int solve_mnl_grid(Ctx& c, const MicroNlArgs& a, int nsolve) {
         return 35;
       }
     }
+    if (w.warm)
+      for (int s = 0; s < cnt; s++) c.mnl_warm_hit[(size_t)h[s].q] = (char)(h[s].warm != 0);
     if (block) {  // the columns' own counts, for mcx_micro_nl_get_tangent (a solve that Newton failed never started them)
       const int64_t ngp = 8 * c.g.nelem;
       MCX_HIP(hipMemcpyAsync(hc.data(), bw.col, sizeof(MnlBlockCol) * 6 * cnt, hipMemcpyDeviceToHost, c.stream));
@@ -1182,7 +1223,9 @@ static int micro_nl_homogenize(Ctx& c) {
     return 34;
   }
   c.mnl_col_its.assign(c.mnl_col_its.size(), 0);
-  if (h[1] == 0) return 0;
+  c.mnl_warm_hit.clear();
+  c.mnl_last_nsolve = h[1];
+  if (h[1] == 0) return mnl_warm_resize(c);
   if (!c.mnl_pool) {
     MCX_HIP(hipMalloc((void**)&c.mnl_pool, (size_t)(c.mnl_cap * bytes)));
     MCX_HIP(hipMemsetAsync(c.mnl_pool, 0, (size_t)(c.mnl_cap * bytes), c.stream));
@@ -1198,6 +1241,7 @@ static int micro_nl_homogenize(Ctx& c) {
   c.mnl_used += h[0];
   if (micro_nl_grid(c)) {
     if (int rc = micro_resize(c, &c.mnl_ws, &c.mnl_ws_bytes, 0)) return rc;
+    if (int rc = mnl_warm_resize(c)) return rc;
     if (int rc = solve_mnl_grid(c, a, h[1])) return rc;
   } else {
     launch_mnl_solve(c, a, h[1]);
@@ -2442,6 +2486,19 @@ int mcx_set_option(void* ctx, const char* name, double value) try {
     c.mnl_apply = (int)value;  // neither the workspace nor the slots follow it: any time; solver 0 and the other laws: no effect
     return 0;
   }
+  if (!std::strcmp(name, "micro_nl_warm")) {  // solver 1 starts a slotted point from its last solution
+    if (value != 0. && value != 1.) {
+      set_error("micro_nl_warm: 0 (off: every cell solve starts as micro_nl_start says) or 1 (on: micro_nl_solver 1 starts a "
+                "slotted point's Newton loop and tangent columns from the slot's last converged solution)");
+      return 1;
+    }
+    c.mnl_warm = (int)value;  // any time; the store follows at the next solve; solver 0 and the other laws: no effect
+    if (!c.mnl_warm) {
+      c.mnl_warm_hit.clear();
+      return micro_resize(c, &c.mnl_warm_store, &c.mnl_warm_store_bytes, 0);
+    }
+    return 0;
+  }
   if (!std::strcmp(name, "pc_mg_dist")) {  // 1: pc_type 1 on a context with a communicator (the distributed hierarchy)
     if (value != 0. && value != 1.) {
       set_error("pc_mg_dist: 0 (pc_type mg on one rank only) or 1 (the hierarchy distributed over the ranks)");
@@ -2945,6 +3002,12 @@ int mcx_apply_args(void* ctx, int argc, const char* const* argv) try {
         return 2;
       }
       value = std::strcmp(v, "fused") ? 0. : 1.;
+    } else if (!std::strcmp(k, "-micro_nl_warm")) {
+      if (std::strcmp(v, "off") && std::strcmp(v, "on")) {
+        set_error(std::string("-micro_nl_warm: off or on, got ") + v);
+        return 2;
+      }
+      value = std::strcmp(v, "on") ? 0. : 1.;
     } else if (!std::strcmp(k, "-pc_mg_precision")) {
       if (std::strcmp(v, "double") && std::strcmp(v, "single")) {
         set_error(std::string("-pc_mg_precision: double or single, got ") + v);

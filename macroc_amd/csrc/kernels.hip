@@ -1871,6 +1871,19 @@ __device__ __forceinline__ double* mnlg_part(const MnlGridWs& w, int s, int q) {
   return w.part + ((size_t)s * MNLG_NPART + q) * (size_t)w.npart;
 }
 
+// option micro_nl_warm 1: field v of a slot's warm record (0 u_w, 1 + l W_l)
+__device__ __forceinline__ double* mnlw_vec(const MnlGridWs& w, int slot, int v, int64_t ndof) {
+  return w.warm + ((size_t)slot * 7 + v) * (size_t)ndof;
+}
+// the warm predictor of interior dof d: u_w + sum_l (eps_l - eps_w,l) W_l, one fma per column, l ascending
+__device__ __forceinline__ double mnl_warm_predict(const double* __restrict__ rec, int64_t ndof, int64_t d,
+                                                   const double (&em)[6], const double (&ew)[6]) {
+  double s = rec[d];
+#pragma unroll
+  for (int l = 0; l < 6; l++) s = fma(em[l] - ew[l], rec[(size_t)(1 + l) * ndof + d], s);
+  return s;
+}
+
 // the batch's records: solve s is point list[base + s], about to take its first state pass
 __global__ void k_mnlg_start(MnlGridWs w, const int* __restrict__ list, const int* __restrict__ slot, int base, int cnt) {
   const int s = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1884,6 +1897,10 @@ __global__ void k_mnlg_start(MnlGridWs w, const int* __restrict__ list, const in
   st.trial = -1;
   st.lam = 1.;
   st.minstep = 1.;
+  if (w.whdr) {  // option micro_nl_warm 1: the solve starts from the slot's record if it is valid, and will overwrite it
+    st.warm = w.whdr[st.slot].valid != 0;
+    w.whdr[st.slot].valid = 0;
+  }
   w.st[s] = st;
 }
 
@@ -1919,6 +1936,15 @@ __global__ __launch_bounds__(MICRO_TPB) void k_mnlg_prep(MicroNlArgs a, MnlGridW
     double em[6];
 #pragma unroll
     for (int l = 0; l < 6; l++) em[l] = eps[l * ngp + st.q];
+    if (st.warm) {  // option micro_nl_warm 1: from the slot's record, whatever micro_nl_start is
+      double ew[6];
+#pragma unroll
+      for (int l = 0; l < 6; l++) ew[l] = w.whdr[st.slot].eps[l];
+      const double* const rec = mnlw_vec(w, st.slot, 0, ndof);
+#pragma unroll
+      for (int r = 0; r < 3; r++) su[3 * (size_t)nd + r] = mnl_warm_predict(rec, ndof, 3 * (int64_t)nd + r, em, ew);
+      return;
+    }
 #pragma unroll
     for (int r = 0; r < 3; r++) su[3 * (size_t)nd + r] = mnl_predict(ufield, ndof, 3 * (int64_t)nd + r, em);
     return;
@@ -2001,6 +2027,7 @@ __device__ __forceinline__ void mnlg_strain(const double* __restrict__ dn, const
 //            stresses, new history, tangent data, trial f), lc >= 0 the stresses C_gp B x of the
 //            column's solution; the tile's six stress sums (times detJ) and its largest f
 //   WHICH 2  the start of a tangent solve: C_gp B x of the boundary values
+//   WHICH 3  option micro_nl_warm 1, the second start pass (MNLG_TSTART2): C_gp B x, x's interior from the record
 template <int WHICH>
 __global__ __launch_bounds__(MICRO_TPB) void k_mnlg_gp(MicroNlArgs a, MnlGridWs w, double* __restrict__ pool) {
   constexpr int P = MG_T + 1, P3 = P * P * P;
@@ -2009,7 +2036,8 @@ __global__ __launch_bounds__(MICRO_TPB) void k_mnlg_gp(MicroNlArgs a, MnlGridWs 
   __shared__ double sred[2 * (MICRO_TPB / 64)];
   const int tid = threadIdx.x, s = blockIdx.y;
   const MnlGridState& st = w.st[s];
-  if (st.stage != (WHICH == 0 ? MNLG_CG : WHICH == 1 ? MNLG_TRANS : MNLG_TSTART)) return;  // the whole workgroup
+  if (st.stage != (WHICH == 0 ? MNLG_CG : WHICH == 1 ? MNLG_TRANS : WHICH == 2 ? MNLG_TSTART : MNLG_TSTART2))
+    return;  // the whole workgroup
   const bool res = WHICH == 1 && st.lc < 0;
   const int n = a.m.n, ne = n - 1, nel = ne * ne * ne, nmgp = 8 * nel, nt = w.ntile, tile = blockIdx.x;
   const int64_t ndof = 3 * (int64_t)n * n * n;
@@ -2143,14 +2171,17 @@ __global__ __launch_bounds__(MICRO_TPB) void k_mnlg_diag(MicroNlArgs a, MnlGridW
 // The node gather over a tile of MG_T^3 nodes: mnl_gather from the slot's work stresses (the node's
 // elements ascending, their Gauss points ascending).  INIT (a Newton step or a tangent solve
 // starts): r = -(the gathered force) on the interior, p = z = D^-1 r, q = 0, the tile's r.z and
-// z.z; else q = the gathered K_T p on the interior and the tile's p.q.
-template <bool INIT>
+// z.z; else q = the gathered K_T p on the interior and the tile's p.q.  WARM: INIT for a column's second
+// start pass alone (option micro_nl_warm 1, stage MNLG_TSTART2).
+template <bool INIT, bool WARM = false>
 __global__ __launch_bounds__(MICRO_TPB) void k_mnlg_gather(MicroNlArgs a, MnlGridWs w, const double* __restrict__ pool) {
   __shared__ double sdn[8 * 24];
   __shared__ double sred[2 * (MICRO_TPB / 64)];
   const int tid = threadIdx.x, s = blockIdx.y;
   const MnlGridState& st = w.st[s];
-  if (INIT ? !((st.stage == MNLG_TRANS && st.lc < 0) || st.stage == MNLG_TSTART) : st.stage != MNLG_CG) return;
+  if (WARM ? st.stage != MNLG_TSTART2
+           : INIT ? !((st.stage == MNLG_TRANS && st.lc < 0) || st.stage == MNLG_TSTART) : st.stage != MNLG_CG)
+    return;
   const int n = a.m.n, ne = n - 1, nel = ne * ne * ne, nt = w.ntile, tile = blockIdx.x;
   const int64_t ndof = 3 * (int64_t)n * n * n;
   const double detJ = 1. / (8. * (double)nel);
@@ -2361,6 +2392,8 @@ __device__ __forceinline__ void mnlg_end(MnlGridState& st, int64_t ngp, int* __r
 //   PHASE 3  a tangent solve starts: norm0, rz; converged at once when the norm is 0
 //   PHASE 4  PHASE 0 under option micro_nl_tangent 1: a converged Newton loop hands the solve to the
 //            block of six columns (stage MNLG_BSTART, the k_mnlb_* kernels below) instead of to column 0
+//   PHASE 5  option micro_nl_warm 1, after a column's second start pass (x's interior from
+//            the record): rz; norm0 stays PHASE 3's; converged at once, with no iteration, or the CG starts
 template <int PHASE_>
 __global__ __launch_bounds__(MICRO_TPB) void k_mnlg_scalar(MicroNlArgs a, MnlGridWs w, int cnt, int64_t ngp,
                                                            double* __restrict__ sig, double* __restrict__ ctan,
@@ -2371,7 +2404,7 @@ __global__ __launch_bounds__(MICRO_TPB) void k_mnlg_scalar(MicroNlArgs a, MnlGri
   __shared__ double sred[2 * (MICRO_TPB / 64)];
   const int tid = threadIdx.x, s = blockIdx.x;
   MnlGridState& st = w.st[s];
-  if (st.stage != (PHASE == 0 ? MNLG_TRANS : PHASE == 3 ? MNLG_TSTART : MNLG_CG)) return;
+  if (st.stage != (PHASE == 0 ? MNLG_TRANS : PHASE == 3 ? MNLG_TSTART : PHASE == 5 ? MNLG_TSTART2 : MNLG_CG)) return;
   const double* const p0 = mnlg_part(w, s, 0);
   const double* const p1 = mnlg_part(w, s, 1);
   double sa = 0., sb = 0.;
@@ -2403,7 +2436,7 @@ __global__ __launch_bounds__(MICRO_TPB) void k_mnlg_scalar(MicroNlArgs a, MnlGri
       if (first) st.nnorm0 = norm0;
       st.fresh = 0;
       st.pend = MNLG_PEND_NONE;
-      if (first && a.nl_start && st.nnorm0 != 0.) {  // the next transition's state pass is at the predictor
+      if (first && (a.nl_start || st.warm) && st.nnorm0 != 0.) {  // the next transition's state pass is at the predictor
         st.pend = MNLG_PEND_PRED;
         return;
       }
@@ -2447,6 +2480,7 @@ __global__ __launch_bounds__(MICRO_TPB) void k_mnlg_scalar(MicroNlArgs a, MnlGri
       for (int k = 0; k < 6; k++) st.col[k * 6 + st.lc] = sg[k];
       if (++st.lc == 6) {
         for (int t = 0; t < 36; t++) ctan[t * ngp + st.q] = 0.5 * (st.col[t] + st.col[(t % 6) * 6 + t / 6]);
+        if (w.whdr) w.whdr[st.slot].valid = 1;  // option micro_nl_warm 1: u and the six columns are in the record
         mnlg_end(st, ngp, its_out, rn_out, fail);
       } else {
         st.stage = MNLG_TSTART;
@@ -2479,12 +2513,24 @@ __global__ __launch_bounds__(MICRO_TPB) void k_mnlg_scalar(MicroNlArgs a, MnlGri
         mnlg_end(st, ngp, its_out, rn_out, fail);
       }
     }
+  } else if (PHASE == 5) {
+    st.rz = sa;
+    if (sqrt(sb) <= a.m.rtol * st.norm0) {
+      st.stage = MNLG_TRANS;  // the record's column solves this one: no iteration
+    } else if (0 < a.m.max_it) {
+      st.stage = MNLG_CG;
+    } else {
+      st.status = 2;
+      mnlg_end(st, ngp, its_out, rn_out, fail);
+    }
   } else {
     st.rz = sa;
     st.norm0 = sqrt(sb);
     st.its = 0;
     if (st.norm0 == 0.) {
       st.stage = MNLG_TRANS;  // the boundary values solve the column: no iteration
+    } else if (st.warm) {
+      st.stage = MNLG_TSTART2;  // option micro_nl_warm 1: the second start pass, from the record's column
     } else if (0 < a.m.max_it) {
       st.stage = MNLG_CG;
     } else {
@@ -2526,6 +2572,32 @@ __global__ __launch_bounds__(MICRO_TPB) void k_mnlg_pupdate(MicroNlArgs a, MnlGr
   if (d >= ndof) return;
   double* const sp = mnlg_vec(w, s, 3, ndof);
   sp[d] = mnlg_vec(w, s, 5, ndof)[d] * mnlg_vec(w, s, 2, ndof)[d] + w.st[s].beta * sp[d];
+}
+
+// option micro_nl_warm 1, one thread per dof, between a slot's warm record and the solve.
+//   SAVE false  a column's second start pass (MNLG_TSTART2): the interior of x from W_lc
+//   SAVE true   column lc has ended (MNLG_TRANS, lc >= 0; its x is about to be overwritten): W_lc = x,
+//               and with column 0 u_w = u, the converged field, and eps_w = the point's strain
+template <bool SAVE>
+__global__ __launch_bounds__(MICRO_TPB) void k_mnlg_warm(MicroNlArgs a, MnlGridWs w, int64_t ngp,
+                                                         const double* __restrict__ eps) {
+  const int s = blockIdx.y;
+  const MnlGridState& st = w.st[s];
+  if (SAVE ? !(st.stage == MNLG_TRANS && st.lc >= 0) : st.stage != MNLG_TSTART2) return;
+  const int n = a.m.n, ne = n - 1, lc = st.lc;
+  const int64_t ndof = 3 * (int64_t)n * n * n, d = (int64_t)blockIdx.x * MICRO_TPB + threadIdx.x;
+  if (SAVE && lc == 0 && d < 6) w.whdr[st.slot].eps[d] = eps[d * ngp + st.q];
+  if (d >= ndof) return;
+  double* const sx = mnlg_vec(w, s, 1, ndof);
+  double* const wl = mnlw_vec(w, st.slot, 1 + lc, ndof);
+  if (SAVE) {
+    wl[d] = sx[d];
+    if (lc == 0) mnlw_vec(w, st.slot, 0, ndof)[d] = mnlg_vec(w, s, 0, ndof)[d];
+    return;
+  }
+  const int nd = (int)(d / 3), i = nd % n, j = (nd / n) % n, k = nd / (n * n);
+  if (i == 0 || j == 0 || k == 0 || i == ne || j == ne || k == ne) return;
+  sx[d] = wl[d];
 }
 
 // ---------------------------------------------------------------------------- the six tangent columns as one block
@@ -2585,6 +2657,8 @@ __global__ __launch_bounds__(MICRO_TPB) void k_mnlb_prep(MicroNlArgs a, MnlGridW
 //            (one pass of MG_T layers, the tangent data read per column: a thread's sum runs over
 //            the layers in k_mnlg_gp<1>'s order)
 //   WHICH 2  the block starts: sigma_l = C_gp B x_l of the boundary values
+//   WHICH 3  option micro_nl_warm 1, the second start pass (MNLG_BSTART2): WHICH 2 for the columns not
+//            done, x_l's interior from the record
 constexpr int MNLB_LZ = 2;
 template <int WHICH>
 __global__ __launch_bounds__(MICRO_TPB, 4) void k_mnlb_gp(MicroNlArgs a, MnlGridWs w, MnlBlockWs bw, double* __restrict__ pool) {
@@ -2596,7 +2670,8 @@ __global__ __launch_bounds__(MICRO_TPB, 4) void k_mnlb_gp(MicroNlArgs a, MnlGrid
   const int tid = threadIdx.x, s = blockIdx.y;
   const MnlGridState& st = w.st[s];
   const bool newton = WHICH == 0 && st.stage == MNLG_CG;
-  if (!newton && st.stage != (WHICH == 0 ? MNLG_BCG : WHICH == 1 ? MNLG_BTRANS : MNLG_BSTART)) return;  // the whole workgroup
+  if (!newton && st.stage != (WHICH == 0 ? MNLG_BCG : WHICH == 1 ? MNLG_BTRANS : WHICH == 2 ? MNLG_BSTART : MNLG_BSTART2))
+    return;  // the whole workgroup
   const MnlBlockCol* const col = bw.col + 6 * (size_t)s;
   const int ncol = newton ? 1 : 6, cpw = 6 / (int)gridDim.z, l0 = (int)blockIdx.z * cpw, l1 = min(l0 + cpw, ncol);
   if (l0 >= l1) return;  // the whole workgroup: grid z splits the six columns, a Newton CG has one
@@ -2630,7 +2705,7 @@ __global__ __launch_bounds__(MICRO_TPB, 4) void k_mnlb_gp(MicroNlArgs a, MnlGrid
     }
 #pragma unroll 1
     for (int l = l0; l < l1; l++) {
-      if (WHICH == 0 && !newton && col[l].done) continue;  // the whole workgroup
+      if ((WHICH == 0 || WHICH == 3) && !newton && col[l].done) continue;  // the whole workgroup
       const double* const src = mnlb_vec(w, bw, s, l, WHICH == 0 ? 3 : 1, ndof);
       double* const sgl = mnlb_sig(ws, bw, s, l, nmgp);
       __syncthreads();  // sdn is written; the column before has been read
@@ -2695,15 +2770,16 @@ __global__ __launch_bounds__(MICRO_TPB, 4) void k_mnlb_gp(MicroNlArgs a, MnlGrid
 // The node gather of the block over a tile of MG_T^3 nodes, column by column from the column's work
 // stresses: k_mnlg_gather's statements.  INIT (the block starts): r_l, p_l = z_l, q_l = 0, the tile's
 // r.z and z.z; else q_l = K_T p_l on the interior and the tile's p.q, for the columns not done (a
-// Newton CG: column 0).
-template <bool INIT>
+// Newton CG: column 0).  WARM: INIT for the second start pass (option micro_nl_warm 1, stage MNLG_BSTART2)
+// of the columns not done.
+template <bool INIT, bool WARM = false>
 __global__ __launch_bounds__(MICRO_TPB) void k_mnlb_gather(MicroNlArgs a, MnlGridWs w, MnlBlockWs bw, double* __restrict__ pool) {
   __shared__ double sdn[8 * 24];
   __shared__ double sred[2 * (MICRO_TPB / 64)];
   const int tid = threadIdx.x, s = blockIdx.y;
   const MnlGridState& st = w.st[s];
   const bool newton = !INIT && st.stage == MNLG_CG;
-  if (!newton && st.stage != (INIT ? MNLG_BSTART : MNLG_BCG)) return;
+  if (!newton && st.stage != (WARM ? MNLG_BSTART2 : INIT ? MNLG_BSTART : MNLG_BCG)) return;
   const MnlBlockCol* const col = bw.col + 6 * (size_t)s;
   const int ncol = newton ? 1 : 6, cpw = 6 / (int)gridDim.z, l0 = (int)blockIdx.z * cpw, l1 = min(l0 + cpw, ncol);
   if (l0 >= l1) return;  // the whole workgroup: grid z splits the six columns, a Newton CG has one
@@ -2722,7 +2798,7 @@ __global__ __launch_bounds__(MICRO_TPB) void k_mnlb_gather(MicroNlArgs a, MnlGri
   const double* const sd = mnlg_vec(w, s, 5, ndof);
 #pragma unroll 1
   for (int l = l0; l < l1; l++) {
-    if (!INIT && !newton && col[l].done) continue;  // the whole workgroup
+    if ((!INIT || WARM) && !newton && col[l].done) continue;  // the whole workgroup
     double y[3] = {0., 0., 0.};
     if (in && !bnd) mnl_gather_sig(mnlb_sig(ws, bw, s, l, nmgp), sdn, n, i, j, k, detJ, y);
     double s0 = 0., s1 = 0.;
@@ -2783,6 +2859,8 @@ __global__ __launch_bounds__(MICRO_TPB, 4) void k_mnlb_apply(MicroNlArgs a, MnlG
 //   PHASE 1  after q = K_T p: pq, alpha per column; !(pq > 0) ends the column unconverged
 //   PHASE 2  after the x / r update: the column's count; converged or out of iterations -> done; else beta
 //   PHASE 3  the block starts (MNLG_BSTART): norm0, rz per column; a column whose norm is 0 is done at once
+//   PHASE 4  option micro_nl_warm 1, after the second start pass (MNLG_BSTART2) of the columns
+//            not done: rz per column, norm0 stays PHASE 3's; a column its record's column solves is done at once
 // PHASE 1 and 2 carry a Newton CG (MNLG_CG) with k_mnlg_scalar's statements on the solve's record,
 // its partials being column 0's.  When the last column is done the solve goes to MNLG_BTRANS.
 template <int PHASE>
@@ -2793,7 +2871,7 @@ __global__ __launch_bounds__(MICRO_TPB) void k_mnlb_scalar(MicroNlArgs a, MnlGri
   const int tid = threadIdx.x, s = blockIdx.x;
   MnlGridState& st = w.st[s];
   const bool newton = (PHASE == 1 || PHASE == 2) && st.stage == MNLG_CG;
-  if (!newton && st.stage != (PHASE == 0 ? MNLG_BTRANS : PHASE == 3 ? MNLG_BSTART : MNLG_BCG)) return;
+  if (!newton && st.stage != (PHASE == 0 ? MNLG_BTRANS : PHASE == 3 ? MNLG_BSTART : PHASE == 4 ? MNLG_BSTART2 : MNLG_BCG)) return;
   MnlBlockCol* const col = bw.col + 6 * (size_t)s;
   if (newton) {
     const double* const p0 = mnlb_part(w, bw, s, 0, 0);
@@ -2837,7 +2915,7 @@ __global__ __launch_bounds__(MICRO_TPB) void k_mnlb_scalar(MicroNlArgs a, MnlGri
 #pragma unroll 1
   for (int l = 0; l < 6; l++) {
     MnlBlockCol& c = col[l];
-    if ((PHASE == 1 || PHASE == 2) && c.done) continue;  // the whole workgroup: c is written after the sums below
+    if ((PHASE == 1 || PHASE == 2 || PHASE == 4) && c.done) continue;  // the whole workgroup: c is written after the sums below
     if (PHASE == 0) {
       double sg[6] = {0., 0., 0., 0., 0., 0.};
 #pragma unroll
@@ -2884,6 +2962,14 @@ __global__ __launch_bounds__(MICRO_TPB) void k_mnlb_scalar(MicroNlArgs a, MnlGri
           c.done = 1;
         }
       }
+    } else if (PHASE == 4) {
+      c.rz = sa;
+      if (sqrt(sb) <= a.m.rtol * c.norm0) {
+        c.done = 1;  // the record's column solves this one: no iteration
+      } else if (!(0 < a.m.max_it)) {
+        c.status = 2;
+        c.done = 1;
+      }
     } else {
       c.rz = sa;
       c.pq = c.alpha = c.beta = 0.;
@@ -2894,7 +2980,7 @@ __global__ __launch_bounds__(MICRO_TPB) void k_mnlb_scalar(MicroNlArgs a, MnlGri
       c.done = 0;
       if (c.norm0 == 0.) {
         c.done = 1;  // the boundary values solve the column: no iteration
-      } else if (!(0 < a.m.max_it)) {
+      } else if (!st.warm && !(0 < a.m.max_it)) {  // option micro_nl_warm 1: PHASE 4 decides
         c.status = 2;
         c.done = 1;
       }
@@ -2913,10 +2999,11 @@ __global__ __launch_bounds__(MICRO_TPB) void k_mnlb_scalar(MicroNlArgs a, MnlGri
       st.status = 2;
     } else {
       for (int t = 0; t < 36; t++) ctan[t * ngp + st.q] = 0.5 * (st.col[t] + st.col[(t % 6) * 6 + t / 6]);
+      if (w.whdr) w.whdr[st.slot].valid = 1;  // option micro_nl_warm 1: u and the six columns are in the record
     }
     mnlg_end(st, ngp, its_out, rn_out, fail);
   } else {
-    st.stage = alldone ? MNLG_BTRANS : MNLG_BCG;
+    st.stage = alldone ? MNLG_BTRANS : (PHASE == 3 && st.warm) ? MNLG_BSTART2 : MNLG_BCG;
   }
 }
 
@@ -2972,6 +3059,29 @@ __global__ __launch_bounds__(MICRO_TPB) void k_mnlb_pupdate(MicroNlArgs a, MnlGr
     double* const sp = mnlb_vec(w, bw, s, l, 3, ndof);
     sp[d] = sd[d] * mnlb_vec(w, bw, s, l, 2, ndof)[d] + (newton ? st.beta : col[l].beta) * sp[d];
   }
+}
+
+// option micro_nl_warm 1 for the block, one thread per dof, k_mnlg_warm's statements.
+//   SAVE false  the second start pass (MNLG_BSTART2), grid z = the column: the interior of x_l from W_l, columns not done
+//   SAVE true   the block has ended (MNLG_BTRANS), grid z = the record's field: W_l = x_l, u_w = u, eps_w
+template <bool SAVE>
+__global__ __launch_bounds__(MICRO_TPB) void k_mnlb_warm(MicroNlArgs a, MnlGridWs w, MnlBlockWs bw, int64_t ngp,
+                                                         const double* __restrict__ eps) {
+  const int s = blockIdx.y, v = blockIdx.z;
+  const MnlGridState& st = w.st[s];
+  if (st.stage != (SAVE ? MNLG_BTRANS : MNLG_BSTART2)) return;
+  const int n = a.m.n, ne = n - 1;
+  const int64_t ndof = 3 * (int64_t)n * n * n, d = (int64_t)blockIdx.x * MICRO_TPB + threadIdx.x;
+  if (SAVE) {
+    if (v == 0 && d < 6) w.whdr[st.slot].eps[d] = eps[d * ngp + st.q];
+    if (d >= ndof) return;
+    mnlw_vec(w, st.slot, v, ndof)[d] = v == 0 ? mnlg_vec(w, s, 0, ndof)[d] : mnlb_vec(w, bw, s, v - 1, 1, ndof)[d];
+    return;
+  }
+  if (bw.col[6 * (size_t)s + v].done || d >= ndof) return;
+  const int nd = (int)(d / 3), i = nd % n, j = (nd / n) % n, k = nd / (n * n);
+  if (i == 0 || j == 0 || k == 0 || i == ne || j == ne || k == ne) return;
+  mnlb_vec(w, bw, s, v, 1, ndof)[d] = mnlw_vec(w, st.slot, 1 + v, ndof)[d];
 }
 
 // One 3x3 block A(node g, node g+d) of the assembled matrix (MatSetValuesLocal(ADD) +
@@ -8258,7 +8368,9 @@ void launch_mnlg_transition(Ctx& c, const MicroNlArgs& a, const MnlGridWs& w, in
   const int64_t ngp = 8 * c.g.nelem;
   const int nn = a.m.n * a.m.n * a.m.n, nt = w.ntile * w.ntile * w.ntile, nnb = (nn + MICRO_TPB - 1) / MICRO_TPB;
   const dim3 tiles(nt, cnt), nodes(nnb, cnt), one(cnt), tpb(MICRO_TPB);
+  const dim3 dofs((3 * nn + MICRO_TPB - 1) / MICRO_TPB, cnt);
   hipLaunchKernelGGL(k_mnlg_prep<false>, nodes, tpb, 0, c.stream, a, w, ngp, c.eps, c.mnl_ufield);
+  if (w.warm) hipLaunchKernelGGL(k_mnlg_warm<true>, dofs, tpb, 0, c.stream, a, w, ngp, c.eps);  // a column that ended -> the record
   hipLaunchKernelGGL(k_mnlg_gp<1>, tiles, tpb, 0, c.stream, a, w, c.mnl_pool);
   hipLaunchKernelGGL(k_mnlg_diag, nodes, tpb, 0, c.stream, a, w, c.mnl_pool);
   hipLaunchKernelGGL(k_mnlg_gather<true>, tiles, tpb, 0, c.stream, a, w, c.mnl_pool);
@@ -8269,6 +8381,13 @@ void launch_mnlg_transition(Ctx& c, const MicroNlArgs& a, const MnlGridWs& w, in
   hipLaunchKernelGGL(k_mnlg_gather<true>, tiles, tpb, 0, c.stream, a, w, c.mnl_pool);
   hipLaunchKernelGGL(k_mnlg_scalar<3>, one, tpb, 0, c.stream, a, w, nt, ngp, c.sig, c.ctan, c.ftrial, c.mnl_its, c.mnl_rn,
                      c.mnl_cnt);
+  if (w.warm) {  // option micro_nl_warm 1: the column's second start pass, x's interior from the record
+    hipLaunchKernelGGL(k_mnlg_warm<false>, dofs, tpb, 0, c.stream, a, w, ngp, c.eps);
+    hipLaunchKernelGGL(k_mnlg_gp<3>, tiles, tpb, 0, c.stream, a, w, c.mnl_pool);
+    hipLaunchKernelGGL((k_mnlg_gather<true, true>), tiles, tpb, 0, c.stream, a, w, c.mnl_pool);
+    hipLaunchKernelGGL(k_mnlg_scalar<5>, one, tpb, 0, c.stream, a, w, nt, ngp, c.sig, c.ctan, c.ftrial, c.mnl_its,
+                       c.mnl_rn, c.mnl_cnt);
+  }
 }
 
 // six launches: stresses of p | q = K_T p, p.q | pq, alpha | x, r, z | its, rel, beta | p
@@ -8330,6 +8449,14 @@ void launch_mnlb_transition(Ctx& c, const MicroNlArgs& a, const MnlGridWs& w, co
   hipLaunchKernelGGL(k_mnlb_gp<2>, tilesgp, tpb, 0, c.stream, a, w, bw, c.mnl_pool);
   hipLaunchKernelGGL(k_mnlb_gather<true>, tiles6, tpb, 0, c.stream, a, w, bw, c.mnl_pool);
   hipLaunchKernelGGL(k_mnlb_scalar<3>, one, tpb, 0, c.stream, a, w, bw, nt, ngp, c.ctan, c.mnl_its, c.mnl_rn, c.mnl_cnt);
+  if (w.warm) {  // option micro_nl_warm 1: the columns' second start pass, then a block that has ended -> the record
+    const int nvb = (3 * nn + MICRO_TPB - 1) / MICRO_TPB;
+    hipLaunchKernelGGL(k_mnlb_warm<false>, dim3(nvb, cnt, 6), tpb, 0, c.stream, a, w, bw, ngp, c.eps);
+    hipLaunchKernelGGL(k_mnlb_gp<3>, tilesgp, tpb, 0, c.stream, a, w, bw, c.mnl_pool);
+    hipLaunchKernelGGL((k_mnlb_gather<true, true>), tiles6, tpb, 0, c.stream, a, w, bw, c.mnl_pool);
+    hipLaunchKernelGGL(k_mnlb_scalar<4>, one, tpb, 0, c.stream, a, w, bw, nt, ngp, c.ctan, c.mnl_its, c.mnl_rn, c.mnl_cnt);
+    hipLaunchKernelGGL(k_mnlb_warm<true>, dim3(nvb, cnt, 7), tpb, 0, c.stream, a, w, bw, ngp, c.eps);
+  }
   hipLaunchKernelGGL(k_mnlb_gp<1>, tiles6, tpb, 0, c.stream, a, w, bw, c.mnl_pool);
   hipLaunchKernelGGL(k_mnlb_scalar<0>, one, tpb, 0, c.stream, a, w, bw, nt, ngp, c.ctan, c.mnl_its, c.mnl_rn, c.mnl_cnt);
 }

@@ -137,6 +137,19 @@ constexpr int MNLG_NPART = 9;  // 0, 1: the dot products; 2 .. 7: the stress sum
 enum { MNLG_CG = 0, MNLG_TRANS = 1, MNLG_TSTART = 2, MNLG_DONE = 3 };
 // what k_mnlg_prep does to u before a Newton solve's next state pass
 enum { MNLG_PEND_NONE = 0, MNLG_PEND_PRED = 1, MNLG_PEND_BACK = 2 };
+// option micro_nl_warm 1: a slot's warm record, the last converged interior field and
+// tangent columns ([slot][7][3 n^3]: u_w, W_0 .. W_5) and its header ([slot]); two more stages,
+// the second start pass of a tangent column (MNLG_TSTART2) or of a block (MNLG_BSTART2)
+enum { MNLG_TSTART2 = 7, MNLG_BSTART2 = 8 };
+struct MnlWarmHdr {
+  double eps[6];  // the macro strain the record belongs to
+  int valid;      // set by a solve that ended converged, cleared when the slot's next solve starts
+  int pad[3];
+};
+static_assert(sizeof(MnlWarmHdr) == 64, "the documented record: 7 x 24 n^3 + 64 bytes");
+inline int64_t mnl_warm_bytes(int n) {  // per slot
+  return (int64_t)sizeof(double) * 7 * 3 * n * n * n + (int64_t)sizeof(MnlWarmHdr);
+}
 struct MnlGridState {
   double rz, pq, alpha, beta, norm0;  // the running CG
   double nnorm0, nrel;                // Newton: the first norm, the last relative one
@@ -151,13 +164,17 @@ struct MnlGridState {
   // options micro_nl_start / micro_nl_ls
   int pend;                      // MNLG_PEND_*: the predictor or a shorter trial is owed to u
   int trial, rejects;            // the trial under test (-1: none; its length is 2^-trial), rejected trials
+  int warm;                      // option micro_nl_warm: the slot's record was valid when the solve began
   double nacc, lam, minstep;     // the norm at the last accepted iterate, 2^-trial, the smallest accepted length
 };
+static_assert(sizeof(MnlGridState) == 8 * 53, "warm sits in the padding: the workspace's size is micro_nl_warm 0's");
 struct MnlGridWs {
   double* vec;
   double* part;
   MnlGridState* st;
   int ntile, npart;
+  double* warm;      // option micro_nl_warm 1: the warm store's fields, else null
+  MnlWarmHdr* whdr;  // and its headers
 };
 inline int64_t mnlg_ws_bytes(int n, int64_t batch) {
   const int64_t ndof = 3 * (int64_t)n * n * n;
@@ -598,6 +615,14 @@ struct Ctx {
   // (k_mnlg_apply / k_mnlb_apply) that never writes the work stresses; the launches of the last mcx_homogenize
   int mnl_apply = 0;
   long long mnl_apply_launches = 0;
+  // option micro_nl_warm: solver 1 starts a slotted point's Newton loop and tangent columns
+  // from the slot's warm record; the store ([mnl_cap] fields, then [mnl_cap] headers) exists while the
+  // option is 1 and a pool exists; mnl_warm_hit: [ngp] the points the last call solved from their record
+  int mnl_warm = 0;
+  double* mnl_warm_store = nullptr;
+  int64_t mnl_warm_store_bytes = 0;
+  std::vector<char> mnl_warm_hit;
+  int mnl_last_nsolve = 0;  // the points the last mcx_homogenize listed (mnl_list)
   int64_t mnl_slots_opt = 0;     // option micro_nl_slots (0: what fits 2 GiB, at most the local Gauss points)
   int64_t mnl_cap = 0, mnl_used = 0;
   double* mnl_ufield = nullptr;  // [6][3 n^3] unit-strain solutions

@@ -140,7 +140,7 @@ static int run(int argc, char** argv) {
   void* ctx = NULL;
   CHK(mcx_init(&o, g_rank, g_size, g_size > 1 ? id : NULL, &ctx));
   /* the flags without an mcx_opts field (-micro_mem, -micro_rtol, -micro_nl_slots, -micro_nl_solver,
-     -micro_nl_start, -micro_nl_ls, -micro_nl_tangent, -micro_nl_apply, ...) */
+     -micro_nl_start, -micro_nl_ls, -micro_nl_tangent, -micro_nl_apply, -micro_nl_warm, ...) */
   CHK(mcx_apply_args(ctx, argc - 1, (const char* const*)argv + 1));
   const char* micro_mem = "lds";
   int micro_grid = 0;    /* -micro_solver grid */

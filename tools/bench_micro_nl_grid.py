@@ -9,6 +9,7 @@ point) and by solver 1 (grid-wide), and the linear-shortcut test alone on a grid
     python tools/bench_micro_nl_grid.py --n 17 --solver 1 --seed 5 --amp 2e-3 --stages 1 1.5 --start 1 --ls 5
     python tools/bench_micro_nl_grid.py --n 10 16 20 --solver 1 --points 8 256 --ka 1e7 --tangent seq block
     python tools/bench_micro_nl_grid.py --n 10 16 20 32 --solver 1 --points 8 --ka 1e7 --apply split fused
+    python tools/bench_micro_nl_grid.py --n 10 16 32 --solver 1 --points 8 --ka 1e7 --tangent seq block --apply fused --warm 0 1
 
 Sphere cells, the tests' load (seed 5; --amp scales it); --ka sets the matrix' hardening modulus (the
 cells' plain Newton gives up on resolved cells with the tests' 1e6, DESIGN §18).  Host clock between two mcx_synchronize;
@@ -18,6 +19,9 @@ measured in the same process; --stages lists load factors with a commit between 
 is the one timed.  A stage whose cells do not converge is reported with the message, not raised.
 --tangent lists values of the option micro_nl_tangent (seq, block), measured in the same process.
 --apply lists values of the option micro_nl_apply (split, fused), measured in the same process.
+--warm lists values of the option micro_nl_warm, measured one after the other in the same
+context: per value the timed stage is homogenised three times, at u, at u again and at u x (1 + 1e-3);
+the second and the third call are reported (ms, Newton and CG maxima, CG sums), one line per value.
 """
 import argparse
 import json
@@ -59,6 +63,23 @@ def timed(m, fn):
     return time.perf_counter() - t0
 
 
+def warm_rows(m, a, rec, u):
+    """option micro_nl_warm: per value, in this context, the calls at u, u and u x (1 + 1e-3); the last two are reported"""
+    for warm in a.warm:
+        m.set_option("micro_nl_warm", warm)  # 0 releases the records; 1 starts with none valid
+        row = dict(rec, warm=warm, converged=True)
+        for name, fac in (("first", 1.0), ("second", 1.0), ("third", 1.0 + 1e-3)):
+            m.set_u(fac * u)
+            m.set_strains()
+            dt = timed(m, m.homogenize)
+            info = m.micro_nl_info()
+            row.update({name + "_ms": dt * 1e3, name + "_newton_max": int(info["newton_its"].max()),
+                        name + "_cg_max": int(info["cg_its"].max()), name + "_cg_sum": int(info["cg_its"].sum()),
+                        name + "_from_record": int((m.micro_nl_warm() == 2).sum())})
+        row.update(solved=int(info["path"].sum()), device_gb=m.get_info()["device_bytes"] / 1e9)
+        print(json.dumps(row), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, nargs="+", default=[10])
@@ -73,6 +94,7 @@ def main():
     ap.add_argument("--ls", type=int, nargs="+", default=[0], help="option micro_nl_ls")
     ap.add_argument("--tangent", nargs="+", default=["seq"], choices=["seq", "block"], help="option micro_nl_tangent")
     ap.add_argument("--apply", nargs="+", default=["split"], choices=["split", "fused"], help="option micro_nl_apply")
+    ap.add_argument("--warm", type=int, nargs="+", default=None, choices=[0, 1], help="option micro_nl_warm: second and third call")
     ap.add_argument("--poll", type=int, default=0, help="option micro_grid_poll (0: leave it alone)")
     ap.add_argument("--linear", type=int, default=0, help="nodes per edge of a macro grid below yield: the linear test alone")
     ap.add_argument("--root", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -109,6 +131,9 @@ def main():
                             m.set_strains()
                             m.homogenize()
                             m.update_vars()
+                        if a.warm is not None:
+                            warm_rows(m, a, rec, a.stages[-1] * u1)
+                            continue
                         m.set_u(a.stages[-1] * u1)
                         m.set_strains()
                         first = timed(m, m.homogenize)
