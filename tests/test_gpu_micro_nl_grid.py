@@ -5,9 +5,11 @@ over the whole device, one workgroup per 8x8x8 tile and one launch per phase, fo
 (test_gpu_micro_nl.py):
     max|x_gpu - x_ref| <= 100 kappa micro_nl_rtol max|x_ref|      (x = sigma, C)
 against the dense numpy reference (kappa from the reference) up to n = 9, against solver 0 up to
-n = 17 (the sum of the two bars), and above n = 20 against what is known in closed form: a cell of
-equal phases is solved by the affine field, so it must give the law of -mat_law plastic.  kappa
-above n = 12 is the dense linear reference's at n = 12 scaled by ((n - 1) / 11)^2.
+n = 17 (the sum of the two bars), and above n = 20, in this file, against what is known in closed
+form: a cell of equal phases is solved by the affine field, so it must give the law of -mat_law
+plastic.  Heterogeneous cells at n = 21 and 26 are judged against a sparse CPU reference's recorded
+results in test_gpu_micro_cells_resolved.py.  kappa above n = 12 is, here, the dense linear
+reference's at n = 12 scaled by ((n - 1) / 11)^2.
 
 Every test sets micro_nl_solver 1.  Measured on an MI355X: DESIGN §18 has the tables.
 """
