@@ -126,6 +126,9 @@ static SpmvTiling spmv_tiling(const Geo& g, int subl) {
 __device__ __forceinline__ int spmv_node(const Geo& g, int TX, int LPB, int nxc, int jgroups, int subl, int& ii,
                                          int& jj, int& kk) {
   const int b = blockIdx.x;
+  // TX = 192 (129 <= nx <= 192) leaves 64 of the 256 threads over: they would take the first 64 nodes
+  // of the next line again, which its own block computes too -- the same y, but twice in the dot partial
+  if ((int)threadIdx.x >= TX * LPB) return -1;
   if (subl < 0) {  // linear order: consecutive blocks = consecutive lines (k, line group, x chunk)
     const int k = b / (jgroups * nxc);
     const int rem = b - k * (jgroups * nxc);
